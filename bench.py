@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--mesh 512] [--window cic] [--dtype f8] [--data uniform|clustered]
+                    [--dump-outputs DIR]
 
 Contract (driver): with --gpus N > 1 it is launched as
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank
@@ -20,6 +21,10 @@ them (rank r: lattice ids [r, r+1) * N^3 / P) and every cycle includes the parti
 exchange (layout.exchange before paint and readout, layout.gather after readout) and
 the FFT's global transposes; `decompose` is done once, outside the timed region, and
 its time is reported separately (exchange reported included/excluded).
+
+--dump-outputs DIR writes what the last timed cycle returned (the readout values and the field of c2r, as .npy;
+a fixed, seeded sample of each when it is large).  The inputs follow from the arguments alone, so two builds can be
+compared output for output.
 
 Extra objects on the JSON line:
   roofline     : dominant kernel's achieved algorithmic GB/s (HIP events on the launch
@@ -43,6 +48,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+# --dump-outputs: at most this many elements per array over all ranks (two fp64 arrays: 32 MB)
+DUMP_MAX_ELEMENTS = 1 << 21
+DUMP_SEED = 2025
 
 
 def algorithmic_bytes(stage, e, pe, nu=1.0, me=0):
@@ -126,7 +134,14 @@ def parse():
                          "512^3 workload): c2 = 256^3 CIC fp64; c3 = 512^3 TSC fp32, gradient readout; c4 = 1024^3 "
                          "mesh / 1024^3 particles CIC fp64 on slabs; c5 = 2048^3 mesh / 2 x 2048^3 clustered particles, "
                          "PCS, per-particle mass, pencils (needs 8 GPUs: 52 GB of particles per GPU)")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last of them returned to its caller as DIR/<name>.npy: '
+                         'readout (the values read out at the particles) and field (the real field of c2r), in the '
+                         'precision of the run; an output larger than DUMP_MAX_ELEMENTS is a fixed, seeded sample of '
+                         'its elements (rank r > 0 of a multi-GPU run: <name>_rank<r>.npy)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     presets = {
         'c2': dict(mesh=256),
         'c3': dict(mesh=512, window='tsc', dtype='f4', gradient=0),
@@ -389,6 +404,8 @@ def main():
         set_b = pos.numel() * pos.element_size()
         work_b = 14 * nloc + 6 * e * N ** 3 // world          # bin lists + mesh, work buffers, halo staging
         nextra = 2 if free_b > 3 * set_b + work_b else 1      # (+1: the temporary of the random step)
+        if args.dump_outputs is not None:
+            nextra = 2        # which set the last step sees must follow from the arguments, not from the memory free
         if world > 1:
             # every rank must build the same number of sets: each costs one collective decompose below, and the
             # local figures (free memory, nloc after --migrate on a clustered set) differ from rank to rank
@@ -458,7 +475,9 @@ def main():
 
     cur_stream = torch.cuda.current_stream()         # (Event.record() without a stream looks it up: ~10 us of host time per mark)
 
-    def cycle(marks=None):
+    last = {}                     # --dump-outputs: the field c2r returned in the last timed step
+
+    def cycle(marks=None, keep=False):
         def mark(i):
             if marks is not None:
                 marks[i].record(cur_stream)
@@ -494,6 +513,8 @@ def main():
         # a fresh 1 GB tensor per cycle occasionally costs a hipMalloc (~20 ms) inside the timed loop
         f = back.readout(pos, gradient=args.gradient, layout=layout, out=result[:len(pos)] if args.count_jitter > 0 else result)
         mark(6)
+        if keep:
+            last['field'] = back
         return f
 
     for _ in range(args.warmup):
@@ -512,12 +533,15 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        f = cycle(ev[k])
+        f = cycle(ev[k], keep=args.dump_outputs is not None and k == args.steps - 1)
     t_issue = time.perf_counter() - t0           # the host has enqueued every cycle (it may have waited inside collectives)
     torch.cuda.synchronize()
     comm.Barrier()
     elapsed = time.perf_counter() - t0
     elapsed = comm.allreduce(elapsed, op='max') if world > 1 else elapsed
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {'readout': f, 'field': last.pop('field').value},
+                     '' if rank == 0 else '_rank%d' % rank, DUMP_MAX_ELEMENTS // world)
 
     comm_line = None
     if records is not None:
@@ -674,6 +698,27 @@ def main():
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, arrays, suffix, limit):
+    """--dump-outputs: each array as path/<name><suffix>.npy, in the float type it was computed in; an array of more
+    than `limit` elements is written as its elements at a fixed, seeded set of flat indices (ascending, 1-d)"""
+    import numpy
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if str(a.dtype).replace('torch.', '') not in ('float32', 'float64'):
+            raise TypeError('--dump-outputs: %s is %s, not float32 / float64' % (name, a.dtype))
+        n = int(numpy.prod(a.shape))
+        if n > limit:
+            flat = numpy.unique(numpy.random.default_rng(DUMP_SEED).integers(0, n, size=limit))
+            where = numpy.unravel_index(flat, tuple(a.shape))
+            if isinstance(a, torch.Tensor):
+                where = tuple(torch.from_numpy(i).to(a.device) for i in where)
+            a = a[where]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        numpy.save(os.path.join(path, name + suffix + '.npy'), a)
 
 
 def baseline_metric():

@@ -51,3 +51,23 @@ def test_bench_other_forms_run():
                  ['--mesh', '128', '--cold-plan', '1'], ['--mesh', '128', '--drift', '2.0']):
         d = run_bench('--steps', '2', '--warmup', '1', '--no-cpu-baseline', *args)
         assert d['value'] > 0 and (d['bin_overflows'] == 0 or '--drift' in args)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the readout values and the c2r field of the last timed step as float .npy files, 64 MB at
+    most, from inputs that do not change between runs (two runs agree up to the order of the paint's additions)"""
+    import numpy
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ('run%d' % k)
+        d = run_bench('--gpus', '1', '--steps', '2', '--warmup', '1', '--mesh', '64', '--no-cpu-baseline',
+                      '--dump-outputs', str(out))
+        assert d['steps'] == 2 and d['ms_per_step'] > 0
+        assert sorted(p.name for p in out.iterdir()) == ['field.npy', 'readout.npy']
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        dumps.append({n: numpy.load(str(out / (n + '.npy'))) for n in ('readout', 'field')})
+    a, b = dumps
+    assert a['readout'].shape == (64 ** 3,) and a['field'].shape == (64, 64, 64)
+    for n in ('readout', 'field'):
+        assert a[n].dtype == numpy.float64 and numpy.isfinite(a[n]).all() and abs(a[n]).max() > 0
+        numpy.testing.assert_allclose(a[n], b[n], rtol=0, atol=1e-10 * abs(a[n]).max())
