@@ -472,6 +472,51 @@ int pmx_apply_transfer(const pmx_transfer *t, int32_t ndim, int32_t elsize, cons
                        const int64_t *shape, const int64_t *start, const int64_t *nmesh,
                        const double *boxsize, void *stream);
 
+/* ---- binned power spectrum (what a caller measures on a painted density: nbodykit's FFTPower; the reference's
+ * TransferFunction.PowerSpectrum, pmesh/transfer.py:133-181, a slab loop of digitize + bincount) ------------------ */
+
+#define PMX_POWER_MAX_KBINS (1 << 20)  /* k bins: any number up to this; a tile takes its bins in windows (LDS) */
+#define PMX_POWER_MAX_MUBINS 64        /* mu bins of the (k, mu) table */
+#define PMX_POWER_MAX_POLES 5          /* multipoles per call */
+#define PMX_POWER_MAX_ELL 8            /* highest multipole order */
+
+typedef struct pmx_power {
+    int32_t nk;                        /* k bins: kedges holds nk + 1 strictly increasing values */
+    int32_t nmu;                       /* 0: no (k, mu) table; else muedges holds nmu + 1 increasing values in [-1, 1] */
+    int32_t npoles;                    /* 0 .. PMX_POWER_MAX_POLES */
+    int32_t poles[PMX_POWER_MAX_POLES];/* their orders ell, 0 .. PMX_POWER_MAX_ELL */
+    int32_t hermitian;                 /* 1: a compressed (r2c) half spectrum — see below */
+    int32_t deconv_pow;                /* divide v by prod_d sinc(w_d/2)^deconv_pow (as pmx_apply_transfer); 0 = off */
+    double volume;                     /* V = prod BoxSize */
+    double los[3];                     /* unit line of sight (mu); logical axis order */
+} pmx_power;
+
+/* Adds the binned sums of the local complex block a (and b; b = NULL: b = a) into `acc`, a device array of float64
+ * that the caller has zeroed (and, on several ranks, sums over the ranks before dividing).  Geometry as in
+ * pmx_apply_transfer: logical shape[0..ndim) at global index start[], byte strides per field, ndim 1..3, elsize 4
+ * (complex64) or 8 (complex128) per component; a and b share the shape and start.  kedges (nk + 1) and muedges
+ * (nmu + 1, or NULL when nmu = 0) are DEVICE arrays of float64.
+ *
+ * Per stored mode, with signed index s_d (global index i_d, minus N_d when i_d >= N_d / 2), all in double:
+ *   k_d = ((s_d * (2 pi / N_d)) * N_d) / L_d,   |k| = sqrt((k_0^2 + k_1^2) + k_2^2),
+ *   mu = (sum_d k_d los_d) / |k| (0 at k = 0),   v = V a conj(b) / prod_d sinc(pi s_d / N_d)^deconv_pow.
+ * A mode is in k bin j when kedges[j] <= |k| < kedges[j + 1] (dropped otherwise), in mu bin m when
+ * muedges[m] <= mu < muedges[m + 1], the last bin closed on the right.  hermitian = 1: a mode whose index along the
+ * last axis is neither 0 nor N/2 stands for itself (weight 1, value v, at mu) and its conjugate (weight 1, value
+ * conj(v), at -mu); every other mode has weight 1.  L_ell are the Legendre polynomials.
+ *
+ * Layout of acc (S = 4 + 2 npoles doubles per k bin, then 5 per (k, mu) cell):
+ *   acc[j*S + 0]            sum w                 acc[j*S + 1]            sum w |k|
+ *   acc[j*S + 2]            sum w Re v            acc[j*S + 3]            sum w Im v
+ *   acc[j*S + 4 + 2p]       sum w Re(v L_ell_p(mu))    acc[j*S + 5 + 2p]  sum w Im(v L_ell_p(mu))
+ *   acc[nk*S + (j*nmu + m)*5 + {0, 1, 2, 3, 4}]   sum w, sum w |k|, sum w mu, sum w Re v, sum w Im v
+ * Sums are added with float atomics: the last bits may differ from run to run.  nk, nmu, npoles above the
+ * PMX_POWER_MAX_* limits return PMX_EUNSUPPORTED. */
+int pmx_power_project(const pmx_power *p, int32_t ndim, int32_t elsize, const void *a, const int64_t *a_strides,
+                      const void *b, const int64_t *b_strides, const int64_t *shape, const int64_t *start,
+                      const int64_t *nmesh, const double *boxsize, const double *kedges, const double *muedges,
+                      double *acc, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

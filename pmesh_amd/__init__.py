@@ -4,6 +4,7 @@
     from pmesh_amd.window import ResampleWindow, Affine, CIC, TSC, PCS
     from pmesh_amd.domain import GridND, Layout
     from pmesh_amd.transfer import Transfer
+    from pmesh_amd.power import power_spectrum     # binned P(k), P(k, mu), multipoles
 
 Host code is Python; all arithmetic is in libpmesh_amd.so (hand-written HIP
 kernels + rocFFT behind the C ABI of include/pmesh_amd.h).  Importing the

@@ -79,6 +79,21 @@ class Transfer(C.Structure):
     ]
 
 
+PMX_POWER_MAX_KBINS = 1 << 20
+PMX_POWER_MAX_MUBINS = 64
+PMX_POWER_MAX_POLES = 5
+PMX_POWER_MAX_ELL = 8
+
+
+class Power(C.Structure):
+    """pmx_power (include/pmesh_amd.h): the bins and options of pmx_power_project"""
+    _fields_ = [
+        ('nk', C.c_int32), ('nmu', C.c_int32), ('npoles', C.c_int32),
+        ('poles', C.c_int32 * PMX_POWER_MAX_POLES), ('hermitian', C.c_int32), ('deconv_pow', C.c_int32),
+        ('volume', C.c_double), ('los', C.c_double * PMX_MAXDIM),
+    ]
+
+
 _P = C.POINTER
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
@@ -156,6 +171,8 @@ DEVICE_ONLY = {
     'rowfft': (C.c_int, [_i32, _i32, _vp, _i64, _i64, _i64, _f64, _i64, _i64, _vp]),
     'slab_pack': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _P(_i64), _i32, _i32, _vp]),
     'slab_unpack': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _P(_i64), _i32, _i32, _vp]),
+    'power_project': (C.c_int, [_P(Power), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
+                                _P(_f64), _vp, _vp, _vp, _vp]),
 }
 
 

@@ -203,6 +203,21 @@ class HipBackend(object):
         self.call('slab_unpack' if inverse else 'slab_pack', src.data_ptr(), dst.data_ptr(), n0, n1, n2,
                   _abi.i64arr(n1_offsets), len(n1_offsets) - 1, elbytes, self.stream())
 
+    # -- binned power spectrum ---------------------------------------------
+    def power_project(self, params, a, b, start, nmesh, boxsize, kedges, muedges, acc):
+        """add the binned sums of the local complex block `a` (times conj(b); b None: the auto spectrum) into the
+        float64 device vector `acc` (layout: include/pmesh_amd.h, pmx_power_project)"""
+        if a.numel() == 0:
+            return
+        es = a.element_size()
+        nd = a.dim()
+        self.call('power_project', C.byref(params), nd, es // 2, a.data_ptr(), _abi.i64arr([s * es for s in a.stride()], 3),
+                  b.data_ptr() if b is not None else None,
+                  _abi.i64arr([s * es for s in b.stride()], 3) if b is not None else None,
+                  _abi.i64arr(a.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3),
+                  kedges.data_ptr(), muedges.data_ptr() if muedges is not None else None, acc.data_ptr(),
+                  self.stream())
+
 
 _current = None
 

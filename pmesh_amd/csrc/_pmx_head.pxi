@@ -50,6 +50,8 @@ cdef extern from "pmesh_amd.h" nogil:
         pass
     ctypedef struct pmx_fft:
         pass
+    ctypedef struct pmx_power:
+        pass
 
 _bound = None
 
