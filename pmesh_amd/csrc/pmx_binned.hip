@@ -576,17 +576,22 @@ __device__ __forceinline__ int row_tile(const pmx_painter &p, const BinGeom &g, 
 #ifndef PMX_LEAN_U
 #define PMX_LEAN_U 4
 #endif
-template <int KIND, int PE, bool WHOLE>
+// ENT: the block-entry form of the plan (bin_entries_kernel): instead of one list slot per row, one 8-byte entry
+// (block, mask) per half-wave and tile — the 32 rows of a half-wave are the aligned block `block`, `mask` the rows of it
+// that belong to the tile.  The same table, ranges and flags, counted in entries; `list` then holds uint2 entries.
+template <int KIND, int PE, bool WHOLE, bool ENT = false>
 __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom &g, const DVec &pos, int64_t n,
                                             uint32_t *counts, uint32_t *flags, const int64_t *offsets,
                                             uint32_t *list, uint32_t *host_flag)
 {
+    uint2 *ents = (uint2 *)list;
     constexpr int U = PMX_LEAN_U, BLOCK_ITERS = BLOCK_ROWS / (TBLOCK * U);
     static_assert(BLOCK_ITERS * TBLOCK * U == BLOCK_ROWS, "rows of a block");
     constexpr uint32_t EMPTY = 0xFFFFFFFFu, DIRECT = 0xFFu;
     __shared__ uint32_t keys[BLOCK_HT], cnt[BLOCK_HT];
     __shared__ int64_t first[BLOCK_HT], last[BLOCK_HT];
     __shared__ uint32_t where[BLOCK_ITERS * U * TBLOCK];
+    __shared__ uint32_t wmask[ENT ? BLOCK_ITERS * U * TBLOCK : 1];     // (ENT: the mask of the entry a leader writes)
     const int lane = threadIdx.x & 63;
     // row (it, u) of this lane within a trip: the U chunks of 64 rows a wave takes follow each other in memory, and its
     // U requests reach a tile's counter back to back: the list keeps the rows of a wave in their order (with the chunks
@@ -645,6 +650,7 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
                     if (t[u] == lt) sm = m;
                     active &= ~m;
                 }
+                if constexpr (ENT) sm &= lane < 32 ? 0xFFFFFFFFull : 0xFFFFFFFF00000000ull;      // (groups within a half-wave)
                 same[u] = sm;
                 leader[u] = t[u] >= 0 ? __ffsll((long long)sm) - 1 : lane;
                 if (u == 0 && ((((uint32_t)(base / (TBLOCK * U))) * 2654435761u) >> 27) == 0) {   // coherence sample, as in bin_count_kernel
@@ -685,11 +691,12 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 if (lead[u]) {
-                    if (e[u] != DIRECT) w[u] = (e[u] << 24) | atomicAdd(&cnt[e[u]], (uint32_t)__popcll(same[u]));
+                    const uint32_t add = ENT ? 1u : (uint32_t)__popcll(same[u]);
+                    if (e[u] != DIRECT) w[u] = (e[u] << 24) | atomicAdd(&cnt[e[u]], add);
                     else {
                         // no room in the table: this group asks the global counter itself
                         w[u] = DIRECT << 24;
-                        bd[u] = atomicAdd(&counts[t[u]], (uint32_t)__popcll(same[u]));
+                        bd[u] = atomicAdd(&counts[t[u]], add);
                     }
                 }
             }
@@ -700,7 +707,22 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
                 const int64_t i = base + lrow(u);
                 const uint32_t rank = (uint32_t)__popcll(same[u] & (((unsigned long long)1 << lane) - 1));
                 uint32_t wh = EMPTY;
-                if (t[u] >= 0) {
+                if (ENT && t[u] >= 0) {
+                    // one entry per group, written by its leader
+                    const uint32_t mask = (uint32_t)(same[u] >> (lane & 32));
+                    if (rank == 0) {
+                        if ((w[u] >> 24) == DIRECT) {
+                            if (list != nullptr) {
+                                const int64_t slot = offsets[t[u]] + (int64_t)bd[u];
+                                if (slot < offsets[t[u] + 1]) ents[slot] = make_uint2((uint32_t)(i >> 5), mask);
+                                else if (atomicOr(&flags[0], 1u) == 0) atomicAdd_system(host_flag, 1u);
+                            }
+                        } else {
+                            wh = w[u];
+                            wmask[(it * U + u) * TBLOCK + threadIdx.x] = mask;
+                        }
+                    }
+                } else if (t[u] >= 0) {
                     if ((w[u] >> 24) == DIRECT) {
                         // (rare) written at once: list[offsets[t] + b + rank]
                         const uint32_t b0 = __shfl(bd[u], leader[u]);
@@ -741,7 +763,10 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
 #endif
                 const uint32_t e = w >> 24;
                 const int64_t slot = first[e] + (w & 0xFFFFFFu);
-                if (slot < last[e]) list[slot] = (uint32_t)i;
+                if (ENT) {
+                    if (slot < last[e]) ents[slot] = make_uint2((uint32_t)(i >> 5), wmask[(it * U + u) * TBLOCK + threadIdx.x]);
+                    else if (atomicOr(&flags[0], 1u) == 0) atomicAdd_system(host_flag, 1u);
+                } else if (slot < last[e]) list[slot] = (uint32_t)i;
                 else if (atomicOr(&flags[0], 1u) == 0) atomicAdd_system(host_flag, 1u);
             }
         }
@@ -785,6 +810,17 @@ __global__ void __launch_bounds__(TBLOCK) bin_repair_lean_kernel(pmx_painter p, 
     // is resident whenever they are; nothing guarantees that on a device shared with other streams or ranks)
     if (*gate == 0) return;
     lean_blocks<KIND, PE, WHOLE>(p, g, pos, n, counts, flags, offsets, list, host_flag);
+}
+
+// The pass of a plan in block-entry form (lean_blocks, ENT): one counter add per (32-row block, tile) instead of a list
+// slot per row.  gate != NULL: the repair after a single pass that overflowed (returns at once unless *gate != 0).
+template <int KIND, int PE, bool WHOLE>
+__global__ void __launch_bounds__(TBLOCK) bin_entries_kernel(pmx_painter p, BinGeom g, DVec pos, int64_t n,
+                                                             uint32_t *counts, uint32_t *flags, const int64_t *offsets,
+                                                             uint2 *ents, uint32_t *host_flag, const uint32_t *gate)
+{
+    if (gate != nullptr && *gate == 0) return;
+    lean_blocks<KIND, PE, WHOLE, true>(p, g, pos, n, counts, flags, offsets, (uint32_t *)ents, host_flag);
 }
 
 // exclusive scan of slot_capacity(counts) -> offsets[nbuckets+1]; one workgroup of NT threads
@@ -1253,7 +1289,9 @@ __device__ __forceinline__ void tile_deposit_quadz(const pmx_painter &p, const B
 // the sum is rounded to 2^-f anyway, and to the canvas type once more for float canvases); void = the reference's
 // arithmetic, operation by operation (NNB / CIC, whose sums are doubles and reproduce the reference bit for bit on
 // exactly summable inputs, the floating-point twin and the deterministic mode)
-template <int KIND, int TTHREADS, bool SORTED, bool FIXED = false, int PE = 0, bool WHOLE = false, typename WF = void>
+// ENT: `list` holds the plan's block entries (uint2 {block, mask}) and `count` is 32 x their number: slot j of the loop
+// is row 32 block + (j & 31) of entry j >> 5, live if its bit is set (the half-waves of the loop are aligned to entries)
+template <int KIND, int TTHREADS, bool SORTED, bool FIXED = false, int PE = 0, bool WHOLE = false, typename WF = void, bool ENT = false>
 __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom &g, const int *t, const DVec &pos,
                                              const DVec &mass, double mass_scalar, const uint32_t *list,
                                              int64_t start, int count, double *lds, double scale = 1.0)
@@ -1292,7 +1330,7 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
     // kernel 14 registers — 69 instead of 55, the fourth workgroup of a CU — and the benchmark's paint 7-12 %
     // (scripts/r06/deal_ab.sh); pm.tile_order, which sorts by tile and NOT by cell, is the remedy a caller has.
     constexpr int W = TTHREADS * UNROLL;
-    constexpr bool CAN_DEAL = !FIXED && !sorted && (W & (W - 1)) == 0;
+    constexpr bool CAN_DEAL = !FIXED && !sorted && !ENT && (W & (W - 1)) == 0;
     bool deal = false;
     if (CAN_DEAL && count >= g.deal_min) {      // (uniform per workgroup)
         __shared__ int deal_flag;
@@ -1332,6 +1370,10 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             int j = j0 + u * TTHREADS;
+            if constexpr (ENT) {
+                const uint2 e = j < count ? ((const uint2 *)list)[start + (j >> 5)] : make_uint2(0u, 0u);
+                idx[u] = ((e.y >> (j & 31)) & 1u) ? (int64_t)e.x * 32 + (j & 31) : -1;
+            } else
             idx[u] = j < count ? (sorted ? start + j : (int64_t)tl[j]) : -1;
         }
 #endif
@@ -1622,13 +1664,14 @@ template <int KIND, bool SORTED, int MODE = 0> constexpr int paint_min_waves()
 // [r5] WHOLE (the block is the whole periodic mesh) and PE (bytes of a position element) are the launcher's to know: one
 // form of the deposit loop per kernel, with its own registers (with all four in one kernel the fixed-point TSC kernel on a
 // double canvas kept per-thread addresses of every form alive across the tile loop and spilled 28 bytes per lane)
-template <int KIND, typename T, int TTHREADS, bool SORTED, int MODE, bool WHOLE, int PE>
-__global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, SORTED, MODE>())) paint_tile_kernel(pmx_painter p, BinGeom g, char *canvas, DVec pos,
-                                                            DVec mass, double mass_scalar,
-                                                            const uint32_t *list, const int64_t *offsets,
-                                                            const uint32_t *counts, T *halo, int overwrite,
-                                                            const double *mstats, int want_odd, const int32_t *dexp,
-                                                            pmx_painter pw)
+// (the body of paint_tile_kernel and, ENT: `list` holds block entries, paint_entries_kernel)
+template <int KIND, typename T, int TTHREADS, bool SORTED, int MODE, bool WHOLE, int PE, bool ENT>
+__device__ __forceinline__ void paint_tile_body(const pmx_painter &p, const BinGeom &g, char *canvas, const DVec &pos,
+                                                const DVec &mass, double mass_scalar,
+                                                const uint32_t *list, const int64_t *offsets,
+                                                const uint32_t *counts, T *halo, int overwrite,
+                                                const double *mstats, int want_odd, const int32_t *dexp,
+                                                const pmx_painter &pw)
 {
     // pw: the painter of the particles (weights, scale bound); p: the layout that is written (MODE 2: the dense
     // integer copy of the block, else the same as pw)
@@ -1690,7 +1733,8 @@ __global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, SORTED, MODE>
         tile_coords(g, tile, t);
         const int64_t start = offsets[tile];
         // (what a crowded tile holds beyond g.chunk entries is painted by paint_heavy_kernel)
-        const int count = counts[tile] < (uint32_t)g.chunk ? (int)counts[tile] : g.chunk;
+        // (ENT: every entry of the tile, 32 slots each; a plan in entry form has no crowded pieces)
+        const int count = ENT ? 32 * (int)counts[tile] : (counts[tile] < (uint32_t)g.chunk ? (int)counts[tile] : g.chunk);
         if (count == 0 && !overwrite && !live) continue;   // nothing to add; uniform per workgroup
         constexpr bool TOUCH = !SORTED && S >= 4;
         uint32_t touched = 0;
@@ -1733,7 +1777,7 @@ __global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, SORTED, MODE>
             __syncthreads();
         }
         if constexpr (TOUCH) list_touch_done(touched);
-        tile_deposit<KIND, TTHREADS, SORTED, FIXED, PE, WHOLE, typename DepositWeights<KIND, T, MODE>::type>(pwr, g, t, pos, mass, mass_scalar, list, start, count, lds, scale);
+        tile_deposit<KIND, TTHREADS, SORTED, FIXED, PE, WHOLE, typename DepositWeights<KIND, T, MODE>::type, ENT>(pwr, g, t, pos, mass, mass_scalar, list, start, count, lds, scale);
         __syncthreads();
         // owned box -> canvas, plain stores in rows of T2 cells
         if constexpr (WHOLE && MODE != 2) {
@@ -1784,6 +1828,32 @@ __global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, SORTED, MODE>
         __syncthreads();
       }
     }
+}
+
+template <int KIND, typename T, int TTHREADS, bool SORTED, int MODE, bool WHOLE, int PE>
+__global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, SORTED, MODE>())) paint_tile_kernel(pmx_painter p, BinGeom g, char *canvas, DVec pos,
+                                                            DVec mass, double mass_scalar,
+                                                            const uint32_t *list, const int64_t *offsets,
+                                                            const uint32_t *counts, T *halo, int overwrite,
+                                                            const double *mstats, int want_odd, const int32_t *dexp,
+                                                            pmx_painter pw)
+{
+    paint_tile_body<KIND, T, TTHREADS, SORTED, MODE, WHOLE, PE, false>(p, g, canvas, pos, mass, mass_scalar, list, offsets, counts,
+                                                                       halo, overwrite, mstats, want_odd, dexp, pw);
+}
+
+// The same for a plan in block-entry form (bin_entries_kernel): the lanes load the rows of their entries straight,
+// no index in front of the position load.
+template <int KIND, typename T, int TTHREADS, int MODE, bool WHOLE, int PE>
+__global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, false, MODE>())) paint_entries_kernel(pmx_painter p, BinGeom g, char *canvas, DVec pos,
+                                                            DVec mass, double mass_scalar,
+                                                            const uint2 *ents, const int64_t *offsets,
+                                                            const uint32_t *counts, T *halo, int overwrite,
+                                                            const double *mstats, int want_odd, const int32_t *dexp,
+                                                            pmx_painter pw)
+{
+    paint_tile_body<KIND, T, TTHREADS, false, MODE, WHOLE, PE, true>(p, g, canvas, pos, mass, mass_scalar, (const uint32_t *)ents, offsets,
+                                                                     counts, halo, overwrite, mstats, want_odd, dexp, pw);
 }
 
 // ---- [r5] 32-bit fixed-point regions for FLOAT canvases (S >= 3) ------------------------------------------------
@@ -2274,7 +2344,8 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
 // general loop pays per trip and this one does not: a wait behind a branch between the two list entries, three
 // position loads with 64-bit strides each (one 12-byte load, or a 16- and an 8-byte one), the element size of the
 // results looked up per store.
-template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE>
+// ENT: `tl` holds block entries (uint2 {block, mask}), `count` is 32 x their number (see tile_deposit)
+template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE, bool ENT = false>
 __device__ __forceinline__ void tile_gather_lean(const pmx_painter &p, const BinGeom &g, const int *t, const DVec &pos,
                                                  char *out, const uint32_t *tl, int count, const T *lds, int ostride)
 {
@@ -2288,8 +2359,15 @@ __device__ __forceinline__ void tile_gather_lean(const pmx_painter &p, const Bin
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             const int j = j0 + u * TTHREADS;
+            if constexpr (ENT) {
+                const uint2 e = ((const uint2 *)tl)[(j < count ? j : count - 1) >> 5];
+                ok[u] = j < count && ((e.y >> (j & 31)) & 1u);
+                id[u] = e.x * 32u + (uint32_t)(j & 31);
+                if (!ok[u]) id[u] = e.x * 32u + (uint32_t)(__ffs(e.y) - 1);      // (a dead slot reads a row of its block: no load behind a branch)
+            } else {
             ok[u] = j < count;
             id[u] = tl[ok[u] ? j : count - 1];            // (an entry beyond the end reads the last one: no load behind a branch)
+            }
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) row[u] = pos_row<PE>(pos, (int64_t)id[u]);
@@ -2344,12 +2422,13 @@ __device__ __forceinline__ void tile_gather_lean(const pmx_painter &p, const Bin
 #ifndef PMX_READOUT_XCD
 #define PMX_READOUT_XCD 1
 #endif
-template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE>
-__global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WAVES : 1)) readout_tile_lean_kernel(pmx_painter p, BinGeom g, const char *canvas,
-                                                                   DVec pos, char *out, const uint32_t *list,
-                                                                   const int64_t *offsets, const uint32_t *counts,
-                                                                   const uint64_t *items, const uint32_t *nitems, uint32_t cap,
-                                                                   int ostride)
+// (the body of readout_tile_lean_kernel and, ENT: `list` holds block entries, readout_entries_kernel)
+template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE, bool ENT>
+__device__ __forceinline__ void readout_lean_body(const pmx_painter &p, const BinGeom &g, const char *canvas,
+                                                  const DVec &pos, char *out, const uint32_t *list,
+                                                  const int64_t *offsets, const uint32_t *counts,
+                                                  const uint64_t *items, const uint32_t *nitems, uint32_t cap,
+                                                  int ostride)
 {
     constexpr int S = Tuned<KIND>::S;
     using Rg = Region<S>;
@@ -2358,11 +2437,17 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
     __shared__ int64_t tab[Rg::R0 + Rg::R1 + Rg::R2];
     {
         // entries of `out` for particles that are in no tile (the common case: none)
-        const int64_t nd = counts[g.ntiles];
-        const uint32_t *dl = list + offsets[g.ntiles];
+        const int64_t nd = (ENT ? 32 : 1) * (int64_t)counts[g.ntiles];
+        const uint32_t *dl = ENT ? list + 2 * offsets[g.ntiles] : list + offsets[g.ntiles];
         for (int64_t j = blockIdx.x * (int64_t)TTHREADS + threadIdx.x; j < nd; j += (int64_t)gridDim.x * TTHREADS) {
-            if (OE == 8) *(double *)(out + (int64_t)dl[j] * ostride) = 0.0;
-            else *(float *)(out + (int64_t)dl[j] * ostride) = 0.0f;
+            int64_t row = 0;
+            if constexpr (ENT) {
+                const uint2 e = ((const uint2 *)dl)[j >> 5];
+                if (!((e.y >> (j & 31)) & 1u)) continue;
+                row = (int64_t)e.x * 32 + (j & 31);
+            } else row = dl[j];
+            if (OE == 8) *(double *)(out + row * ostride) = 0.0;
+            else *(float *)(out + row * ostride) = 0.0f;
         }
     }
     const int64_t nh = *nitems < cap ? *nitems : cap;
@@ -2376,7 +2461,7 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
         }
         const int64_t start = offsets[tile] + first;
         const int64_t left = (int64_t)counts[tile] - first;
-        const int count = left < g.chunk ? (int)left : g.chunk;
+        const int count = (ENT ? 32 : 1) * (left < g.chunk ? (int)left : g.chunk);
         if (count <= 0) continue;
         int t[3];
         tile_coords(g, tile, t);
@@ -2390,9 +2475,31 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
             lds[r * Rg::template gpitch<T>() + c] = (o0 | o1 | o2) >= 0 ? *(const T *)(canvas + (o0 + o1 + o2)) : (T)0;
         }
         __syncthreads();
-        tile_gather_lean<KIND, T, TTHREADS, PE, OE, WHOLE>(p, g, t, pos, out, list + start, count, lds, ostride);
+        tile_gather_lean<KIND, T, TTHREADS, PE, OE, WHOLE, ENT>(p, g, t, pos, out, ENT ? list + 2 * start : list + start, count, lds, ostride);
         __syncthreads();
     }
+}
+
+template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE>
+__global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WAVES : 1)) readout_tile_lean_kernel(pmx_painter p, BinGeom g, const char *canvas,
+                                                                   DVec pos, char *out, const uint32_t *list,
+                                                                   const int64_t *offsets, const uint32_t *counts,
+                                                                   const uint64_t *items, const uint32_t *nitems, uint32_t cap,
+                                                                   int ostride)
+{
+    readout_lean_body<KIND, T, TTHREADS, PE, OE, WHOLE, false>(p, g, canvas, pos, out, list, offsets, counts, items, nitems, cap, ostride);
+}
+
+// The same for a plan in block-entry form (bin_entries_kernel): rows loaded straight from their entries, results stored
+// to consecutive rows.  (Such a plan has no crowded pieces: items are read but there are none.)
+template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE>
+__global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WAVES : 1)) readout_entries_kernel(pmx_painter p, BinGeom g, const char *canvas,
+                                                                   DVec pos, char *out, const uint2 *ents,
+                                                                   const int64_t *offsets, const uint32_t *counts,
+                                                                   const uint64_t *items, const uint32_t *nitems, uint32_t cap,
+                                                                   int ostride)
+{
+    readout_lean_body<KIND, T, TTHREADS, PE, OE, WHOLE, true>(p, g, canvas, pos, out, (const uint32_t *)ents, offsets, counts, items, nitems, cap, ostride);
 }
 
 // [r6] The same for up to PMX_MAXFIELDS canvases of ONE block geometry read at the same positions, the results side by
@@ -2462,12 +2569,15 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
 // so it also hands the build's measurement of the row order (flags[1..2]) to the host's mapped slot (no copy node)
 static __global__ void __launch_bounds__(TBLOCK) heavy_items_kernel(const uint32_t *counts, int64_t ntiles, int chunk,
                                                              uint64_t *items, uint32_t *nitems, uint32_t cap,
-                                                             const uint32_t *flags, uint32_t *host_measure)
+                                                             const uint32_t *flags, uint32_t *host_measure,
+                                                             uint32_t crowd = 0xFFFFFFFFu, uint32_t *host_crowded = nullptr)
 {
     if (host_measure != nullptr && blockIdx.x == 0 && threadIdx.x < 2)
         __hip_atomic_store(&host_measure[threadIdx.x], flags[1 + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (int64_t tile = blockIdx.x * (int64_t)TBLOCK + threadIdx.x; tile < ntiles; tile += (int64_t)gridDim.x * TBLOCK) {
         const uint32_t c = counts[tile];
+        // (a hint for the next build: a crowded tile makes a plan keep the index list, whose crowded pieces are split)
+        if (c > crowd && host_crowded != nullptr) __hip_atomic_store(host_crowded, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (c > (uint32_t)chunk) {
             const uint32_t extra = (c - 1) / (uint32_t)chunk;
             const uint32_t base = atomicAdd(nitems, extra);
@@ -2673,7 +2783,57 @@ static int halo_cells(int S)
 
 using namespace pmx;
 
+int plan_to_list(pmx_binplan *pl, hipStream_t st);       // (part 1; called by the consumers of the index list)
+
 #if PMX_PART_PLAN
+// ---- a plan in block-entry form turned into the index list, for the consumers that read the list ----------------------
+// rows per bucket: the set bits of its entries
+static __global__ void __launch_bounds__(TBLOCK) entry_rows_kernel(const uint2 *ents, const int64_t *offsets, const uint32_t *counts,
+                                                            int64_t nb, uint32_t *rows)
+{
+    for (int64_t b = blockIdx.x * (int64_t)TBLOCK + threadIdx.x; b < nb; b += (int64_t)gridDim.x * TBLOCK) {
+        uint32_t r = 0;
+        for (uint32_t k = 0; k < counts[b]; k++) r += (uint32_t)__popc(ents[offsets[b] + k].y);
+        rows[b] = r;
+    }
+}
+// the rows of every bucket's entries, in entry order, into the list ranges `loff`
+static __global__ void __launch_bounds__(TBLOCK) entry_fill_kernel(const uint2 *ents, const int64_t *offsets, const uint32_t *counts,
+                                                            const int64_t *loff, int64_t nb, uint32_t *list)
+{
+    for (int64_t b = blockIdx.x * (int64_t)TBLOCK + threadIdx.x; b < nb; b += (int64_t)gridDim.x * TBLOCK) {
+        int64_t slot = loff[b];
+        for (uint32_t k = 0; k < counts[b]; k++) {
+            const uint2 e = ents[offsets[b] + k];
+            for (uint32_t m = e.y; m; m &= m - 1) list[slot++] = e.x * 32u + (uint32_t)(__ffs(m) - 1);
+        }
+    }
+}
+
+// The plan leaves the block-entry form for good (the builds that follow make the index list): a consumer that reads
+// the list — a deterministic paint, a readout in exact arithmetic or of several fields, pmx_binplan_order — was served.
+int plan_to_list(pmx_binplan *pl, hipStream_t st)
+{
+    if (!pl->blocks) return PMX_OK;
+    const int64_t nb = pl->g.ntiles + 1;
+    int rc = plan_ensure((void **)&pl->rows, &pl->cap_rows, (size_t)(nb + 1) * 4); if (rc) return rc;
+    rc = plan_ensure((void **)&pl->loff, &pl->cap_loff, (size_t)(nb + 1) * 8); if (rc) return rc;
+    const unsigned grid = grid_for(nb, TBLOCK, 1024);
+    entry_rows_kernel<<<grid, TBLOCK, 0, st>>>((const uint2 *)pl->ents, pl->offsets, pl->counts, nb, pl->rows);
+    bin_scan_kernel<<<1, 1024, 0, st>>>(pl->rows, nb, pl->loff, pl->cursor, nullptr, nullptr, pl->slack);
+    entry_fill_kernel<<<grid, TBLOCK, 0, st>>>((const uint2 *)pl->ents, pl->offsets, pl->counts, pl->loff, nb, pl->list);
+    PMX_HIP_CHECK(hipMemcpyAsync(pl->counts, pl->rows, (size_t)nb * 4, hipMemcpyDeviceToDevice, st));
+    PMX_HIP_CHECK(hipMemcpyAsync(pl->offsets, pl->loff, (size_t)(nb + 1) * 8, hipMemcpyDeviceToDevice, st));
+    pl->g.chunk = pl->chunk_rows;
+    PMX_HIP_CHECK(hipMemsetAsync(pl->nheavy, 0, 4, st));
+    heavy_items_kernel<<<grid_for(pl->g.ntiles, TBLOCK, 1024), TBLOCK, 0, st>>>(pl->counts, pl->g.ntiles, pl->g.chunk, pl->heavy_items,
+                                                                              pl->nheavy, (uint32_t)pl->cap_heavy, pl->flags, nullptr);
+    PMX_HIP_CHECK(hipGetLastError());
+    pl->blocks = false;
+    pl->blocks_off = true;
+    return PMX_OK;
+}
+
 extern "C" int pmx_binplan_create(pmx_binplan **plan)
 {
     PMX_REQUIRE(plan != nullptr, PMX_EINVAL, "plan pointer is NULL");
@@ -2684,6 +2844,12 @@ extern "C" int pmx_binplan_create(pmx_binplan **plan)
 extern "C" int pmx_binplan_configure(pmx_binplan *pl, int32_t form)
 {
     PMX_REQUIRE(pl != nullptr, PMX_EINVAL, "plan is NULL");
+    if (form >= 0 && (form & ~0x3FF) == 0 && (form >> 8) != 0) {
+        // PMX_BINPLAN_BLOCKS_NEVER / _ALWAYS (| the form, or alone for auto): whether the plan may take block entries
+        const int pref = (form >> 8) == 1 ? 0 : ((form >> 8) == 2 ? 1 : -1);
+        form = (form & 0xFF) == 0xFF ? -1 : (form & 0xFF);
+        if (pl->blocks_pref != pref) { pl->blocks_pref = pref; pl->have_history = false; pl->blocks_off = false; pl->blocks_drops = 0; }
+    }
     PMX_REQUIRE(form >= -1 && form <= 2, PMX_EINVAL, "form must be -1 (auto), 0 (tiles) or 2 (tiles, chunk rebuild)");
     PMX_REQUIRE(form != 1, PMX_EUNSUPPORTED, "form 1 (the walk kernels of rounds 2-3) is no longer part of the library");
     if (pl->form != form) pl->have_history = false;
@@ -2780,6 +2946,7 @@ static __global__ void __launch_bounds__(TBLOCK) order_copy_kernel(const uint32_
 }
 extern "C" int pmx_binplan_order(pmx_binplan *pl, int64_t *order, void *stream)
 {
+    if (pl != nullptr && pl->built) { const int rc = plan_to_list(pl, (hipStream_t)stream); if (rc) return rc; }
     PMX_REQUIRE(pl && pl->built, PMX_EINVAL, "bin plan is not built");
     PMX_REQUIRE(order != nullptr || pl->npart == 0, PMX_EINVAL, "order is NULL");
     if (pl->npart == 0) return PMX_OK;
@@ -2821,6 +2988,9 @@ extern "C" int pmx_binplan_destroy(pmx_binplan *pl)
     if (pl->dscratch) (void)hipFree(pl->dscratch);
     if (pl->dhalo) (void)hipFree(pl->dhalo);
     if (pl->heavy_items) (void)hipFree(pl->heavy_items);
+    if (pl->ents) (void)hipFree(pl->ents);
+    if (pl->rows) (void)hipFree(pl->rows);
+    if (pl->loff) (void)hipFree(pl->loff);
     delete pl;
     return PMX_OK;
 }
@@ -2995,6 +3165,7 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         pl->host_flag[1] = 0;      // particles a tile kernel found outside the region their list entry names (pmx_binplan_stale)
         pl->host_flag[2] = 0;      // [2..3]: the last finished build's measurement of the row order (heavy_items_kernel)
         pl->host_flag[3] = 0;
+        pl->host_flag[4] = 0;      // [4]: a build of this plan saw a crowded tile (heavy_items_kernel; the next builds keep the list)
     }
     uint32_t *measure_out = nullptr;
     pl->g.stale = pl->host_flag + 1;
@@ -3048,14 +3219,49 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // 9.50 against 7.06 / 7.67 / 10.58 / 11.04; only rows in no order at all (63) gain: 22.8 against 14.4.
         // Two thresholds: a plan takes the copy above 61.5 and gives it up below 58 (position sets on either side of ONE
         // threshold made the plan start over every step: 11.1 ms at 8 cells of jitter against 9.5 in either form).
-        auto incoherent = [&](double breaks, double rows, bool has_copy) { return breaks * 64.0 > (has_copy ? PMX_SORTED_DROP_BREAKS : PMX_SORTED_TAKE_BREAKS) * rows; };
-        if (reuse && pl->sort_pref < 0 && pl->host_groups[2] == (uint32_t)npart && pl->host_groups[1] > 4096 &&
-            incoherent(pl->host_groups[0], (double)pl->host_groups[1], pl->sorted) != pl->sorted)
-            reuse = false;       // the order of the rows changed its character since the plan was built: start over
-        if (!reuse) pl->sorted = false;
 #ifndef PMX_LEAN_BIN
 #define PMX_LEAN_BIN 1
 #endif
+#ifndef PMX_BLOCKS_TAKE_BREAKS
+#define PMX_BLOCKS_TAKE_BREAKS 6.0
+#endif
+#ifndef PMX_BLOCKS_DROP_BREAKS
+#define PMX_BLOCKS_DROP_BREAKS 10.0
+#endif
+        auto incoherent = [&](double breaks, double rows, bool has_copy) { return breaks * 64.0 > (has_copy ? PMX_SORTED_DROP_BREAKS : PMX_SORTED_TAKE_BREAKS) * rows; };
+        // Block entries (bin_entries_kernel) for rows in a coherent order: CIC on the whole periodic mesh, dense rows of
+        // doubles (the benchmark's form; everything else keeps the list).  A plan takes them when the last build measured
+        // at most PMX_BLOCKS_TAKE_BREAKS breaks of the tile sequence per 64 rows and gives them up above
+        // PMX_BLOCKS_DROP_BREAKS (two thresholds, as for the copy); a crowded tile seen by the last build keeps the list
+        // (its pieces are split over workgroups; a tile in entry form is one workgroup's).
+        bool whole_p = true;
+        for (int d = 0; d < 3; d++) whole_p = whole_p && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];
+        // (sticky: a plan that has seen a crowded tile, or has given the entries up twice — position sets that alternate
+        // between orders — keeps the list for good rather than paying a two-pass build at every change of form)
+        const bool crowded = *(volatile uint32_t *)(pl->host_flag + 4) != 0 || pl->blocks_drops >= 2;
+        const bool blocks_ok = PMX_LEAN_BIN && dense && whole_p && pos->elsize == 8 && p.kind == PMX_TUNED_CIC && pl->form != 2 &&
+                               pl->sort_pref != 1 && !pl->deterministic && !pl->blocks_off && npart < ((int64_t)1 << 32);
+        bool blocks_now = false;
+        if (blocks_ok) {
+            if (pl->blocks_pref == 1) blocks_now = true;
+            else if (pl->blocks_pref < 0 && pl->have_measure && pl->host_groups[1] > 4096 && !crowded)
+                blocks_now = (double)pl->host_groups[0] * 64.0 <= (pl->blocks ? PMX_BLOCKS_DROP_BREAKS : PMX_BLOCKS_TAKE_BREAKS) * (double)pl->host_groups[1];
+        }
+        if (pl->blocks && !blocks_now) pl->blocks_drops++;
+        if (blocks_now != pl->blocks) reuse = false;        // (the ranges of the previous build count the other unit)
+        if (blocks_now) {
+            const size_t nent = list_entries(np1 + np1 / 8);
+            if (pl->cap_ents < nent * 8) {
+                if (pl->ents) (void)hipFree(pl->ents);
+                pl->ents = nullptr; pl->cap_ents = 0;
+                rc = plan_ensure(&pl->ents, &pl->cap_ents, nent * 8); if (rc) return rc;
+                reuse = false;
+            }
+        }
+        if (reuse && pl->sort_pref < 0 && pl->host_groups[2] == (uint32_t)npart && pl->host_groups[1] > 4096 &&
+            incoherent(pl->host_groups[0], (double)pl->host_groups[1], pl->sorted) != pl->sorted)
+            reuse = false;       // the order of the rows changed its character since the plan was built: start over
+        if (!reuse || blocks_now) pl->sorted = false;
 #ifndef PMX_REPAIR_GRID
 #define PMX_REPAIR_GRID 512      // workgroups of the gated repair, resident at once (measured 128 / 256 / 512: the launch that returns at once 4.7 us each; the repair of 512^3 rows 5.3 / 3.4 / 2.6 ms)
 #endif
@@ -3090,7 +3296,24 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         };
         pl->last_reuse = reuse;
         pl->builds[reuse ? 0 : 1]++;
-        if (reuse) {
+        pl->blocks = blocks_now;
+        if (blocks_now) {
+            // [r7] block entries: one pass that emits an entry per (32-row block, tile); the gated repair is the same
+            // pass into ranges laid out from the exact counts (every pass adds to a counter before it looks at the range)
+            const int64_t nblocks = (npart + BLOCK_ROWS - 1) / BLOCK_ROWS;
+            const unsigned bgrid = (unsigned)(nblocks < 65535 * 8 ? nblocks : 65535 * 8);
+            const unsigned rgrid = bgrid < PMX_REPAIR_GRID ? bgrid : PMX_REPAIR_GRID;
+            uint2 *ents = (uint2 *)pl->ents;
+            if (reuse) {
+                bin_entries_kernel<PMX_TUNED_CIC, 8, true><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, ents, pl->host_flag, nullptr);
+                bin_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, g.ntiles + 1, pl->offsets, pl->cursor, pl->flags, pl->counts, pl->slack);
+                bin_entries_kernel<PMX_TUNED_CIC, 8, true><<<rgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, ents, pl->host_flag, pl->flags);
+            } else {
+                bin_entries_kernel<PMX_TUNED_CIC, 8, true><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, nullptr, pl->host_flag, nullptr);
+                bin_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, nbuckets, pl->offsets, pl->cursor, nogate, pl->counts, pl->slack);
+                bin_entries_kernel<PMX_TUNED_CIC, 8, true><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, ents, pl->host_flag, nullptr);
+            }
+        } else if (reuse) {
             // single pass into the previous slot ranges; if a tile overflowed (flags[0]) the
             // exact two-pass build below runs, otherwise its kernels return at once.  Whether the
             // plan carries the tile-ordered copy was decided by its first build.
@@ -3187,9 +3410,13 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
     } else {
         bin_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, nbuckets, pl->offsets, pl->cursor, nullptr, nullptr, pl->slack);
     }
+    pl->chunk_rows = g.chunk;
+    if (pl->blocks) pl->g.chunk = 1 << 30;       // (no pieces: a tile in entry form is one workgroup's)
     if (npart > 0)
-        heavy_items_kernel<<<grid_for(g.ntiles, TBLOCK, 1024), TBLOCK, 0, st>>>(pl->counts, g.ntiles, g.chunk, pl->heavy_items,
-                                                                               pl->nheavy, (uint32_t)pl->cap_heavy, pl->flags, measure_out);
+        heavy_items_kernel<<<grid_for(g.ntiles, TBLOCK, 1024), TBLOCK, 0, st>>>(pl->counts, g.ntiles, pl->g.chunk, pl->heavy_items,
+                                                                               pl->nheavy, (uint32_t)pl->cap_heavy, pl->flags, measure_out,
+                                                                               pl->blocks ? (uint32_t)(g.chunk / 32) : (uint32_t)g.chunk,
+                                                                               pl->host_flag + 4);
     PMX_HIP_CHECK(hipGetLastError());
     pl->built = true;
     pl->have_history = npart > 0;
@@ -3217,6 +3444,12 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
     const int64_t nwork = (g.ntiles / ntw) * ((ntw + ZSEG - 1) / ZSEG);   // segments of tiles along the walk axis
     unsigned pgrid = (unsigned)(nwork < 65535 * 8 ? nwork : 65535 * 8);
     T *halo = (T *)pl->halo;
+    const bool dense_rows = pos.stride1 == pos.elsize && pos.stride0 == 3 * pos.elsize;
+    if (pl->blocks && (pl->deterministic || pos.elsize != 8 || !dense_rows)) {
+        rc = plan_to_list(pl, st);     // (paint_entries_kernel takes the floating-point form of dense rows of doubles)
+        if (rc) return rc;
+    }
+    const bool ents = pl->blocks;
     const int sorted = pl->sorted ? 1 : 0;
     if (sorted) {
         // stream the plan's copy of the positions (dense rows of 3 elements, list order)
@@ -3296,7 +3529,12 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
                     else halo_merge_kernel<S_, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, halo, pl->counts, overwrite); } while (0)
     switch (p.kind) {
     case PMX_TUNED_NNB: PT(PMX_TUNED_NNB); break;
-    case PMX_TUNED_CIC: PT(PMX_TUNED_CIC); HM(2); break;
+    case PMX_TUNED_CIC:
+        if (ents) paint_entries_kernel<PMX_TUNED_CIC, T, TileThreads<PMX_TUNED_CIC, T>::paint, 0, true, 8><<<pgrid, TileThreads<PMX_TUNED_CIC, T>::paint, 0, st>>>(
+                      p, g, (char *)canvas, pos, mass, ms, (const uint2 *)pl->ents, pl->offsets, pl->counts, halo, overwrite, mstats, 0, dexp, p);
+        else PT(PMX_TUNED_CIC);
+        HM(2);
+        break;
     case PMX_TUNED_TSC: PT(PMX_TUNED_TSC); HM(3); break;
     default: PT(PMX_TUNED_PCS); HM(4); break;
     }
@@ -3311,13 +3549,13 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
 #undef PT32L
 #undef HM
     // the pieces of crowded tiles (none for a uniform batch: the kernel then returns at once)
-    const unsigned hgrid = (unsigned)(pl->cap_heavy < 1024 ? pl->cap_heavy : 1024);
+    const unsigned hgrid = ents ? 0u : (unsigned)(pl->cap_heavy < 1024 ? pl->cap_heavy : 1024);
 #define PH3(K, TT, MD, ODD, PP, CV) do { if (sorted) paint_heavy_kernel<K, TT, TileThreads<K, TT>::paint, true, MD><<<hgrid, TileThreads<K, TT>::paint, 0, st>>>(PP, g, (char *)(CV), pos, mass, ms, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, mstats, ODD, dexp, p); \
                    else paint_heavy_kernel<K, TT, TileThreads<K, TT>::paint, false, MD><<<hgrid, TileThreads<K, TT>::paint, 0, st>>>(PP, g, (char *)(CV), pos, mass, ms, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, mstats, ODD, dexp, p); } while (0)
 #define PH(K) do { if (run_fixed && det) PH3(K, double, 2, 0, pd, pl->dscratch); \
                    else if (run_fixed) PH3(K, T, 1, 0, p, canvas); \
                    if (run_float) PH3(K, T, 0, (run_fixed ? 1 : 0), p, canvas); } while (0)
-    switch (p.kind) {
+    if (hgrid > 0) switch (p.kind) {
     case PMX_TUNED_NNB: PH(PMX_TUNED_NNB); break;
     case PMX_TUNED_CIC: PH(PMX_TUNED_CIC); break;
     case PMX_TUNED_TSC: PH(PMX_TUNED_TSC); break;
@@ -3461,6 +3699,12 @@ extern "C" int pmx_readout_binned(pmx_binplan *pl, const pmx_painter *p_, const 
     const BinGeom &g = pl->g;
     hipStream_t st = (hipStream_t)stream;
     DVec dout = dvec(out), dpos = dvec(pos);
+    if (pl->blocks) {
+        // readout_entries_kernel: the lean form (relaxed arithmetic, dense rows of doubles, a dense result vector or column)
+        const bool fits = pl->exact == 0 && dpos.elsize == 8 && dpos.stride1 == 8 && dpos.stride0 == 24 && dout.stride0 >= dout.elsize &&
+                          dout.stride0 % dout.elsize == 0 && dout.stride0 < (1 << 20);
+        if (!fits) { const int rc = plan_to_list(pl, st); if (rc) return rc; }
+    }
     // particles that touch no local cell are in no tile: they read 0
     const int sorted = pl->sorted ? 1 : 0;
     const DVec caller_out = dout;
@@ -3496,7 +3740,9 @@ extern "C" int pmx_readout_binned(pmx_binplan *pl, const pmx_painter *p_, const 
 #ifdef PMX_GENERAL_FORMS_ONLY
     whole_r = false;       // (a build switch for measurements, right results: what the forms for blocks of any shape cost on a whole mesh)
 #endif
-#define RLL(K, T, PE_, OE_, WH) readout_tile_lean_kernel<K, T, TileThreads<K, T>::readout, PE_, OE_, WH><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data), pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, (int)dout.stride0)
+#define RLL(K, T, PE_, OE_, WH) do { if (K == PMX_TUNED_CIC && PE_ == 8 && WH && pl->blocks) \
+        readout_entries_kernel<PMX_TUNED_CIC, T, TileThreads<PMX_TUNED_CIC, T>::readout, 8, OE_, true><<<grid, TileThreads<PMX_TUNED_CIC, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data), (const uint2 *)pl->ents, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, 0u, (int)dout.stride0); \
+    else readout_tile_lean_kernel<K, T, TileThreads<K, T>::readout, PE_, OE_, WH><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data), pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, (int)dout.stride0); } while (0)
 #define RLW(K, T, PE_, OE_) do { if (whole_r) RLL(K, T, PE_, OE_, true); else RLL(K, T, PE_, OE_, false); } while (0)
 #define RLO(K, T, PE_) do { if (dout.elsize == 8) RLW(K, T, PE_, 8); else RLW(K, T, PE_, 4); } while (0)
 #define RL(K, T) do { if (dpos.elsize == 8) RLO(K, T, 8); else RLO(K, T, 4); } while (0)
@@ -3577,6 +3823,7 @@ extern "C" int pmx_readout_binned_multi(pmx_binplan *pl, const pmx_painter *p_, 
     if (pl->npart == 0) return PMX_OK;
     PMX_REQUIRE(vec_ok(pos), PMX_EINVAL, "pos");
     pmx_painter p = *p_;
+    if (pl->blocks) { const int rc = plan_to_list(pl, (hipStream_t)stream); if (rc) return rc; }      // (the multi-field readout reads the list)
     const BinGeom &g = pl->g;
     hipStream_t st = (hipStream_t)stream;
     const DVec dout = dvec(out), dpos = dvec(pos);

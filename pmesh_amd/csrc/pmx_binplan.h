@@ -185,6 +185,19 @@ struct pmx_binplan {
     void *dhalo = nullptr;             // its halo staging (8 bytes per cell whatever the canvas type)
     size_t cap_dhalo = 0;
     int32_t chunk = 1 << 30;           // list entries per piece
+    // Block entries (bin_entries_kernel): rows in a coherent order described by 8-byte entries {32-row block, mask of its
+    // rows in the tile} instead of a 4-byte list slot per row.  counts / offsets / the ranges then count entries.
+    int blocks_pref = -1;              // -1: chosen from the measured row order; 0 / 1: forced (where the form applies)
+    bool blocks = false;               // this build is in block-entry form
+    int blocks_drops = 0;              // builds that left the entry form ('auto'): from two on the plan keeps the list
+    bool blocks_off = false;           // a consumer needed the list (plan_to_list): the builds that follow make the list
+    void *ents = nullptr;              // the entries (uint2), ranges as `offsets` names
+    size_t cap_ents = 0;
+    uint32_t *rows = nullptr;          // plan_to_list: rows per bucket, and their ranges
+    size_t cap_rows = 0;
+    int64_t *loff = nullptr;
+    size_t cap_loff = 0;
+    int32_t chunk_rows = 1 << 30;      // the list form's g.chunk (a plan in block-entry form splits no tile)
     // history for the single-pass build: the slot ranges of the previous build of the same
     // geometry and particle count are reused (particles move little between time steps)
     bool have_history = false;

@@ -81,6 +81,11 @@ _SORTS = {'auto': -1, 'never': 0, 'always': 1}
 # A tile-ordered copy of the positions inside the plan, for rows without spatial coherence
 # (include/pmesh_amd.h: pmx_binplan_sorted): 'auto' (measured by the first build), 'never', 'always'.
 SORTED = os.environ.get('PMESH_AMD_SORTED', 'auto')
+# Block entries in the bin plan (csrc/pmx_binned.hip: bin_entries_kernel) — rows in a coherent order described by
+# 32-row blocks and a mask per tile instead of an index per row; CIC on a whole periodic mesh, dense rows of doubles:
+# 'auto' (from the row order measured by the previous build), 'never', 'always' (where the form applies).
+BLOCKS = os.environ.get('PMESH_AMD_BLOCKS', 'auto')
+_BLOCKS = {'auto': 3, 'never': 1, 'always': 2}
 # Deterministic paint: True makes every paint that the tile kernels can serve (3-d, tuned window, native support,
 # no hsml) bit-reproducible — independent of the order of arrival of anything and of the order of the rows: all
 # sums are 64-bit integers in units of 2^-f (include/pmesh_amd.h: pmx_binplan_deterministic), rounded once into the
@@ -165,7 +170,7 @@ class _BinCache(object):
         self._told = {}       # id(entry) -> [(deterministic, exact), (form, sorted)] as last told to the library
 
     def _key(self, pos, painter):
-        return (pos.data_ptr(), version_of(pos), tuple(pos.shape), pos.stride(), pos.dtype, WALK, SORTED,
+        return (pos.data_ptr(), version_of(pos), tuple(pos.shape), pos.stride(), pos.dtype, WALK, SORTED, BLOCKS,
                 painter.kind, tuple(painter.scale), tuple(painter.translate),
                 tuple(painter.period), tuple(painter.size))
 
@@ -234,9 +239,9 @@ class _BinCache(object):
             be.call('binplan_exact', e[1], want[1])
             opts[0] = want
         if build:
-            form = (_FORMS[WALK], _SORTS[SORTED])
+            form = (_FORMS[WALK], _SORTS[SORTED], _BLOCKS[BLOCKS])
             if opts[1] != form:
-                be.call('binplan_configure', e[1], form[0])
+                be.call('binplan_configure', e[1], (form[2] << 8) | (form[0] & 0xFF))
                 be.call('binplan_sorted', e[1], form[1], None)
                 opts[1] = form
 
