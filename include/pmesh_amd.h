@@ -225,6 +225,10 @@ int pmx_binplan_stale(pmx_binplan *plan, uint32_t *count);
  * a particle count within an eighth of the previous one: a time-stepping caller, also one whose particles migrate
  * between ranks) / in two passes (the first build, another geometry or count, the back-off after an overflow). */
 int pmx_binplan_builds(pmx_binplan *plan, uint32_t *single_pass, uint32_t *two_pass);
+/* Which form the plan is in now: in_entry_form = 1 while its last build is in the block-entry form (32-row blocks and
+ * a mask per tile; 0 once a consumer of the index list has turned it into the list), drops = the builds of its current
+ * history that gave the entry form up (from two on the plan keeps the list).  Host state only: no synchronisation. */
+int pmx_binplan_blocks(pmx_binplan *plan, int32_t *in_entry_form, uint32_t *drops);
 /* [r6] The order of the rows that a built plan holds, for the caller: order[k] (npart int64 of device memory) = the row that
  * stands k-th when the rows are taken tile by tile — inside a tile in the order of the rows themselves — and the rows
  * that touch no local cell last.  A time-stepping caller re-sorts its particle arrays with it every few steps

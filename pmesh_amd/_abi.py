@@ -135,6 +135,7 @@ DEVICE_ONLY = {
     'binplan_overflows': (C.c_int, [_vp, _P(C.c_uint32)]),
     'binplan_stale': (C.c_int, [_vp, _P(C.c_uint32)]),
     'binplan_builds': (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32)]),
+    'binplan_blocks': (C.c_int, [_vp, _P(_i32), _P(C.c_uint32)]),
     'binplan_sorted': (C.c_int, [_vp, _i32, _P(_i32)]),
     'binplan_order': (C.c_int, [_vp, _vp, _vp]),
     'binplan_supported': (C.c_int, [_P(Painter), _i64]),

@@ -2570,14 +2570,24 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
 static __global__ void __launch_bounds__(TBLOCK) heavy_items_kernel(const uint32_t *counts, int64_t ntiles, int chunk,
                                                              uint64_t *items, uint32_t *nitems, uint32_t cap,
                                                              const uint32_t *flags, uint32_t *host_measure,
-                                                             uint32_t crowd = 0xFFFFFFFFu, uint32_t *host_crowded = nullptr)
+                                                             uint32_t crowd = 0xFFFFFFFFu, uint32_t *host_crowded = nullptr,
+                                                             const uint2 *ents = nullptr, const int64_t *offsets = nullptr,
+                                                             uint32_t crowd_rows = 0xFFFFFFFFu)
 {
     if (host_measure != nullptr && blockIdx.x == 0 && threadIdx.x < 2)
         __hip_atomic_store(&host_measure[threadIdx.x], flags[1 + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (int64_t tile = blockIdx.x * (int64_t)TBLOCK + threadIdx.x; tile < ntiles; tile += (int64_t)gridDim.x * TBLOCK) {
         const uint32_t c = counts[tile];
         // (a hint for the next build: a crowded tile makes a plan keep the index list, whose crowded pieces are split)
-        if (c > crowd && host_crowded != nullptr) __hip_atomic_store(host_crowded, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // (entry form: `crowd` entries hold at most crowd_rows rows; past it the tile's rows are counted — entries of rows
+        // in no order hold one row each, and such a tile is no more crowded than in the list)
+        bool crowded = c > crowd && host_crowded != nullptr;
+        if (crowded && ents != nullptr) {
+            uint32_t r = 0;
+            for (uint32_t k = 0; k < c && r <= crowd_rows; k++) r += (uint32_t)__popc(ents[offsets[tile] + k].y);
+            crowded = r > crowd_rows;
+        }
+        if (crowded) __hip_atomic_store(host_crowded, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (c > (uint32_t)chunk) {
             const uint32_t extra = (c - 1) / (uint32_t)chunk;
             const uint32_t base = atomicAdd(nitems, extra);
@@ -2905,6 +2915,14 @@ extern "C" int pmx_binplan_builds(pmx_binplan *pl, uint32_t *single_pass, uint32
     return PMX_OK;
 }
 
+extern "C" int pmx_binplan_blocks(pmx_binplan *pl, int32_t *in_entry_form, uint32_t *drops)
+{
+    PMX_REQUIRE(pl != nullptr && in_entry_form != nullptr && drops != nullptr, PMX_EINVAL, "NULL argument");
+    *in_entry_form = pl->built && pl->blocks ? 1 : 0;
+    *drops = (uint32_t)pl->blocks_drops;
+    return PMX_OK;
+}
+
 // ---- [r6] the plan's order of the rows, for the caller ------------------------------------------------------------------
 // order[k] = the row that stands k-th when the rows are taken tile by tile (tiles in index order, inside a tile in the
 // order the bin pass met them — the order of the rows themselves, block by block), the rows that touch no local cell
@@ -3093,6 +3111,17 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
     bool reuse = pl->built && pl->have_history && dn * 8 <= pl->npart && npart > 0 &&
                  same_geometry(p, pl->painter) && pl->g.ntiles == g.ntiles &&
                  (!pl->sorted || pl->cap_copy >= pl->cap_list * 3 * (size_t)pos->elsize);
+    // A build that starts a new history (the first; another geometry; a count outside an eighth of the last; the form or
+    // the preferences changed through pmx_binplan_configure / _sorted) serves another particle set: what the plan learnt
+    // from the old one about the block-entry form — a consumer of the list, the drops, a crowded tile — is forgotten.
+    // Inside one history it sticks.
+    const bool fresh = !(pl->built && pl->have_history && dn * 8 <= pl->npart && npart > 0 && same_geometry(p, pl->painter) &&
+                         pl->g.ntiles == g.ntiles);
+    if (fresh) {
+        pl->blocks_off = false;
+        pl->blocks_drops = 0;
+        if (pl->host_flag) pl->host_flag[4] = 0;
+    }
     if (pl->host_flag) {
         uint32_t seen = *(volatile uint32_t *)pl->host_flag;   // stale at worst: a hint only
         if (seen != pl->seen_overflows) {
@@ -3416,7 +3445,8 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         heavy_items_kernel<<<grid_for(g.ntiles, TBLOCK, 1024), TBLOCK, 0, st>>>(pl->counts, g.ntiles, pl->g.chunk, pl->heavy_items,
                                                                                pl->nheavy, (uint32_t)pl->cap_heavy, pl->flags, measure_out,
                                                                                pl->blocks ? (uint32_t)(g.chunk / 32) : (uint32_t)g.chunk,
-                                                                               pl->host_flag + 4);
+                                                                               pl->host_flag + 4, pl->blocks ? (const uint2 *)pl->ents : nullptr,
+                                                                               pl->offsets, (uint32_t)g.chunk);
     PMX_HIP_CHECK(hipGetLastError());
     pl->built = true;
     pl->have_history = npart > 0;

@@ -259,6 +259,17 @@ class _BinCache(object):
                 n += int(c.value)
         return n
 
+    def block_plans(self, be):
+        """(in block-entry form, drops) of every built plan, in pool order (include/pmesh_amd.h: pmx_binplan_blocks;
+        host state, no synchronisation)"""
+        out = []
+        for e in self.entries:
+            if e[3]:
+                f, d = C.c_int32(0), C.c_uint32(0)
+                be.call('binplan_blocks', e[1], C.byref(f), C.byref(d))
+                out.append((bool(f.value), int(d.value)))
+        return out
+
     def _warn_if_stale(self, be, e):
         """A plan is reused for a tensor at the same address and version (torch counts in-place operations).  Rows
         rewritten behind that — a kernel of the caller's own through data_ptr(), a numpy view of shared memory — leave

@@ -30,23 +30,55 @@ def hip():
     from pmesh_amd import backend
     backend.reset()
     b = backend.get()
-    old, oldw, olds, olde = window.BINNED, window.WALK, window.SORTED, window.EXACT
+    old, oldw, olds, olde, oldb = window.BINNED, window.WALK, window.SORTED, window.EXACT, window.BLOCKS
     yield b
-    window.BINNED, window.WALK, window.SORTED, window.EXACT = old, oldw, olds, olde
+    window.BINNED, window.WALK, window.SORTED, window.EXACT, window.BLOCKS = old, oldw, olds, olde, oldb
     window.clear_bin_cache()
     backend.reset()
 
 
-@pytest.fixture(params=['tiles', 'sorted', 'chunks'])
+@pytest.fixture(params=['tiles', 'sorted', 'chunks', 'blocks'])
 def form(request, hip):
     """the forms of the binned kernels: the tile kernels through the index list
-    (csrc/pmx_binned.hip), the tile kernels on the plan's tile-ordered copy of the positions, and the
+    (csrc/pmx_binned.hip), the tile kernels on the plan's tile-ordered copy of the positions, the
     tile kernels with the chunk form of the single-pass rebuild (bin_count_kernel<MODE 1> instead of
-    bin_block_kernel, which 'tiles' takes)"""
+    bin_block_kernel, which 'tiles' takes), and the block entries (bin_entries_kernel, paint_entries_kernel,
+    readout_entries_kernel) wherever they apply — CIC on a whole periodic mesh with dense rows of doubles; every other
+    batch of that variant is served by the list, and check_form asserts which"""
     window.WALK = {'chunks': 'chunks'}.get(request.param, 'never')
     window.SORTED = 'always' if request.param == 'sorted' else 'never'
-    window.clear_bin_cache()
+    window.BLOCKS = 'always' if request.param == 'blocks' else 'never'
+    window.bin_cache().destroy(hip)          # (plan state of earlier tests is sticky: start from none)
     yield request.param
+    window.bin_cache().destroy(hip)
+
+
+def clear_plans():
+    """forget the cached batches; under BLOCKS = 'always' the plans themselves, whose history a consumer of the index
+    list has taken out of the entry form (pmx_binplan_blocks)"""
+    if window.BLOCKS == 'always':
+        from pmesh_amd import backend
+        window.bin_cache().destroy(backend.get())
+    else:
+        window.clear_bin_cache()
+
+
+def entries_apply(name, shape, period, ptype='f8'):
+    """where the block-entry form serves: CIC, the whole periodic mesh, dense rows of doubles"""
+    return name == 'cic' and tuple(shape) == tuple(period) and ptype == 'f8'
+
+
+def check_form(form, entries):
+    """in the 'blocks' variant: the plan used last is in block-entry form exactly when the form applies (read through
+    pmx_binplan_blocks before any consumer of the index list has run)"""
+    if form != 'blocks':
+        return
+    from pmesh_amd import backend
+    cache = window.bin_cache()
+    built = [e for e in cache.entries if e[3]]
+    last = max(range(len(built)), key=lambda i: built[i][4])
+    assert cache.block_plans(backend.get())[last][0] == entries, 'expected the %s' % (
+        'block-entry form' if entries else 'index list')
 
 
 def both(W, fn):
@@ -54,7 +86,7 @@ def both(W, fn):
     window.BINNED = 'never'
     a = fn()
     window.BINNED = 'always'
-    window.clear_bin_cache()
+    clear_plans()
     b = fn()
     return a, b
 
@@ -66,6 +98,8 @@ CASES = [
     ((24, 48, 64), (96, 48, 64), 1.0, (-32.0, 0.0, 0.0)),                # slab-local block of a bigger mesh
     ((24, 40, 70), (0, 0, 0), 1.0, 0.0),                                 # non periodic, ragged tiles
     ((20, 48, 45), (64, 0, 128), 1.0, (0.0, 2.0, -5.0)),                 # mixed
+    ((24, 32, 96), (24, 32, 96), (0.25, 0.5, 1.5), (1.5, -0.75, 3.0)),   # whole periodic, 3 x 2 x 3 tiles
+    ((16, 32, 64), (16, 32, 64), 1.0, 0.0),                              # whole periodic, the smallest: 2 x 2 x 2 tiles
 ]
 
 
@@ -98,6 +132,7 @@ def test_binned_equals_direct(hip, form, oracle, name, case):
                     return c.cpu().numpy()
                 d, b = both(W, paint)
                 assert_binned_ran()
+                check_form(form, entries_apply(name, shape, period, ptype))
                 s = max(1.0, abs(d).max())
                 assert_allclose(b, d, rtol=0, atol=tol * s)
                 if ptype == 'f8' and diffdir is None and dt == 'f8':
@@ -112,8 +147,10 @@ def test_binned_equals_direct(hip, form, oracle, name, case):
     # overwrite == zero + accumulate; accumulate really accumulates
     pos = torch.from_numpy(pos_h).to(hip.device)
     window.BINNED = 'always'
+    clear_plans()
     c1 = torch.full(shape, 7.0, dtype=torch.float64, device=hip.device)
     W.paint(c1, pos, transform=aff, _overwrite=True)
+    check_form(form, entries_apply(name, shape, period))
     c2 = torch.zeros(shape, dtype=torch.float64, device=hip.device)
     W.paint(c2, pos, transform=aff)
     assert_allclose(c1.cpu().numpy(), c2.cpu().numpy(), rtol=0, atol=1e-12 * max(1, float(c2.abs().max())))
@@ -147,11 +184,12 @@ def test_default_readout_within_tolerance_of_the_exact_form(hip, form, oracle, n
             for diffdir in (None, 1):
                 want = oracle.Window(W.kind).readout(field_h, ph, diffdir=diffdir, transform=oaff)
                 window.EXACT = False
-                window.clear_bin_cache()
+                clear_plans()
                 got = W.readout(field, pos, diffdir=diffdir, transform=aff).cpu().numpy()
                 assert_binned_ran()
+                check_form(form, entries_apply(name, shape, period, ptype))
                 window.EXACT = True
-                window.clear_bin_cache()
+                clear_plans()
                 exact = W.readout(field, pos, diffdir=diffdir, transform=aff).cpu().numpy()
                 assert_array_equal(exact, want)
                 sc = numpy.atleast_1d(numpy.asarray(scale, dtype='f8'))
@@ -188,10 +226,11 @@ def test_sparse_clusters_across_tile_faces(hip, form, oracle, name, period):
         want = base.copy()
         oracle.Window(W.kind).paint(want, pos_h, mass=mass_h, transform=oaff)
         window.BINNED = 'always'
-        window.clear_bin_cache()
+        clear_plans()
         c = torch.from_numpy(base.copy()).to(hip.device)
         W.paint(c, pos, mass=mass, transform=aff)                       # accumulate
         assert_binned_ran()
+        check_form(form, entries_apply(name, shape, period))
         # (the cubic weights carry a 1/6: exact sums only for CIC and TSC)
         check = assert_array_equal if name != 'pcs' else (lambda a, b: assert_allclose(a, b, rtol=0, atol=1e-12))
         check(c.cpu().numpy(), want)
@@ -314,6 +353,7 @@ def test_binned_dyadic_bit_exact(hip, form, oracle, name):
     W.paint(c, torch.from_numpy(pos_h).to(hip.device), mass=torch.from_numpy(mass_h).to(hip.device),
             transform=Affine(3, period=N))
     assert_binned_ran()
+    check_form(form, entries_apply(name, (N, N, N), (N, N, N)))
     assert_array_equal(c.cpu().numpy(), want)
 
 
@@ -619,12 +659,14 @@ def test_rebuild_from_history_and_overflow(hip, form, oracle, name):
     pass into the slot ranges of its previous build (time-stepping callers).  Results must
     not depend on that: (1) slightly moved particles (ranges hold), (2) a completely different
     distribution of the same size (ranges overflow -> exact two-pass build on the device),
-    (3) the builds after the overflow (back-off), all against the oracle; readout bit-exact."""
-    window.EXACT = True            # the bit-identical form of the binned readout (pmx_binplan_exact)
+    (3) the builds after the overflow (back-off), all against the oracle; readout bit-exact.  In the 'blocks' variant
+    the readout is the default one (the exact form reads the index list: the plan would leave the entry form for good),
+    within the bound of test_default_readout_within_tolerance_of_the_exact_form, and CIC keeps the entries throughout."""
+    window.EXACT = form != 'blocks'    # the bit-identical form of the binned readout (pmx_binplan_exact)
     W = windows[name]
     N, n = 64, 60000
     window.BINNED = 'always'
-    window.clear_bin_cache()
+    clear_plans()
     aff = Affine(3, period=N)
     oaff = oracle.Affine(3, period=N)
     rs = numpy.random.RandomState(11)
@@ -640,11 +682,18 @@ def test_rebuild_from_history_and_overflow(hip, form, oracle, name):
         c = torch.zeros((N, N, N), dtype=torch.float64, device=hip.device)
         W.paint(c, pos, transform=aff)
         assert_binned_ran()
+        check_form(form, entries_apply(name, (N, N, N), (N, N, N)))
         want = numpy.zeros((N, N, N))
         oracle.Window(W.kind).paint(want, ph, transform=oaff)
         assert_allclose(c.cpu().numpy(), want, rtol=0, atol=1e-12 * abs(want).max(), err_msg='step %d' % k)
         got = W.readout(field, pos, transform=aff).cpu().numpy()
-        assert_array_equal(got, oracle.Window(W.kind).readout(field_h, ph, transform=oaff), err_msg='step %d' % k)
+        want = oracle.Window(W.kind).readout(field_h, ph, transform=oaff)
+        if window.EXACT:
+            assert_array_equal(got, want, err_msg='step %d' % k)
+        else:
+            assert_allclose(got, want, rtol=0, atol=1e-13 * abs(field_h).max(), err_msg='step %d' % k)
+            assert_array_equal(got == 0, want == 0)
+        check_form(form, entries_apply(name, (N, N, N), (N, N, N)))
         if k == 0:
             serving = [e[1].value for e in window.bin_cache().entries if e[3]]
         # one plan (the pool keeps earlier ones) served every step
@@ -738,11 +787,13 @@ def test_random_geometries_over_moving_particles(hip, seed):
 
 def test_rebuild_drops_and_nonperiodic(hip, form, oracle):
     """history rebuilds with particles that touch no local cell (their own bucket) on a
-    non-periodic sub-block: dropped particles read 0 and paint nothing"""
+    non-periodic sub-block: dropped particles read 0 and paint nothing.  (TSC on a block that is not the whole mesh:
+    the 'blocks' variant is served by the list, and asserts so; test_rebuild_drops_on_the_whole_periodic_mesh is the
+    entry form's.)"""
     window.EXACT = True            # the bit-identical form of the binned readout (pmx_binplan_exact)
     W = windows['tsc']
     window.BINNED = 'always'
-    window.clear_bin_cache()
+    clear_plans()
     N, n = 48, 30000
     aff = Affine(3, translate=[-8, 0, -4], period=[0, 96, 0])
     oaff = oracle.Affine(3, translate=[-8, 0, -4], period=[0, 96, 0])
@@ -756,11 +807,48 @@ def test_rebuild_drops_and_nonperiodic(hip, form, oracle):
         c = torch.zeros((N, N, N), dtype=torch.float64, device=hip.device)
         W.paint(c, pos, transform=aff)
         assert_binned_ran()
+        check_form(form, False)
         want = numpy.zeros((N, N, N))
         oracle.Window(W.kind).paint(want, ph, transform=oaff)
         assert_allclose(c.cpu().numpy(), want, rtol=0, atol=1e-12 * max(1.0, abs(want).max()))
         got = W.readout(field, pos, transform=aff).cpu().numpy()
         assert_array_equal(got, oracle.Window(W.kind).readout(field_h, ph, transform=oaff))
+
+
+def test_rebuild_drops_on_the_whole_periodic_mesh(hip, form, oracle):
+    """history rebuilds of CIC on the whole periodic mesh (where the 'blocks' variant takes the entries) with rows in no
+    cell: NaN rows inside 32-row blocks read 0 and paint nothing, rows far outside wrap; paint against the oracle,
+    the default readout within its bound"""
+    W = windows['cic']
+    window.BINNED = 'always'
+    clear_plans()
+    N, n = 64, 40000
+    aff = Affine(3, scale=0.5, translate=0.25, period=N)
+    oaff = oracle.Affine(3, scale=0.5, translate=0.25, period=N)
+    rs = numpy.random.RandomState(6)
+    field_h = rs.normal(size=(N, N, N))
+    field = torch.from_numpy(field_h).to(hip.device)
+    pos = torch.zeros((n, 3), dtype=torch.float64, device=hip.device)
+    ph = numpy.sort(rs.uniform(0, 2 * N, size=(n, 3)), axis=0)
+    for k in range(4):
+        ph = ph + rs.normal(0, 0.3, size=(n, 3))
+        q = ph.copy()
+        q[k::13 + k] = numpy.nan
+        q[5::31] += 2 * N * rs.randint(-50, 50, size=(len(q[5::31]), 3))
+        pos.copy_(torch.from_numpy(q))
+        ok = numpy.isfinite(q).all(axis=1)
+        c = torch.zeros((N, N, N), dtype=torch.float64, device=hip.device)
+        W.paint(c, pos, transform=aff)
+        assert_binned_ran()
+        check_form(form, True)
+        want = numpy.zeros((N, N, N))
+        oracle.Window(W.kind).paint(want, q[ok], transform=oaff)
+        assert_allclose(c.cpu().numpy(), want, rtol=0, atol=1e-12 * max(1.0, abs(want).max()), err_msg='step %d' % k)
+        got = W.readout(field, pos, transform=aff).cpu().numpy()
+        check_form(form, True)
+        assert (got[~ok] == 0).all()
+        assert_allclose(got[ok], oracle.Window(W.kind).readout(field_h, q[ok], transform=oaff), rtol=0,
+                        atol=1e-13 * abs(field_h).max(), err_msg='step %d' % k)
 
 
 @pytest.mark.parametrize('name,dtype', [('cic', 'f8'), ('tsc', 'f4')])
@@ -857,7 +945,7 @@ def test_time_stepping_cycles_equal_oracle(hip, oracle, N, name, dtype, tol):
     from pmesh_amd.pm import ParticleMesh
     from pmesh_amd.transfer import Transfer
     window.BINNED = 'auto'
-    window.clear_bin_cache()
+    window.bin_cache().destroy(hip)           # (no plan state of earlier tests: see test_bin_blocks.py)
     L = 1000.0
     tdt = torch.float64 if dtype == 'f8' else torch.float32
     pos = torch.empty((N ** 3, 3), dtype=tdt, device=hip.device)
@@ -874,6 +962,12 @@ def test_time_stepping_cycles_equal_oracle(hip, oracle, N, name, dtype, tol):
         rho = pm.paint(pos)
         assert_binned_ran()
         served += [e[1].value for e in window.bin_cache().entries if e[3] and e[2] is pos]
+        if window.BLOCKS == 'auto':
+            # the benchmark's form: the first build measures the (lattice) row order, the next ones take the block
+            # entries (CIC, dense rows of doubles, the whole periodic mesh) — asserted before the readout runs
+            built = [e for e in window.bin_cache().entries if e[3]]
+            forms = [f for e, f in zip(built, window.bin_cache().block_plans(hip)) if e[2] is pos]
+            assert forms == [(step > 0 and name == 'cic' and dtype == 'f8', 0)], (step, forms)
         f = rho.r2c(out=Ellipsis).c2r(out=Ellipsis, transfer=Transfer.dx1(0)).readout(pos)
         real, ck, back, want = oracle.pm_cycle(N, L, pos.cpu().numpy(), kind='tuned' + name, transfer=t, dtype=dtype)
         err = abs(f.cpu().numpy() - want).max() / abs(want).max()

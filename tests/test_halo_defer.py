@@ -31,12 +31,24 @@ def hip():
     from pmesh_amd import backend
     backend.reset()
     b = backend.get()
-    old = (window.BINNED, pmod.HALO_DEFER, _fft.L3_BLOCK_BYTES)
+    old = (window.BINNED, pmod.HALO_DEFER, _fft.L3_BLOCK_BYTES, window.BLOCKS)
     window.BINNED = 'always'
     yield b
-    window.BINNED, pmod.HALO_DEFER, _fft.L3_BLOCK_BYTES = old
+    window.BINNED, pmod.HALO_DEFER, _fft.L3_BLOCK_BYTES, window.BLOCKS = old
     window.clear_bin_cache()
     backend.reset()
+
+
+def use_blocks(hip):
+    """the benchmark's paint form: block entries (paint_entries_kernel with defer = 1) on fresh plans"""
+    window.BLOCKS = 'always'
+    window.bin_cache().destroy(hip)
+
+
+def assert_entry_form(hip):
+    """every built plan is in block-entry form (pmx_binplan_blocks)"""
+    forms = window.bin_cache().block_plans(hip)
+    assert forms and all(f for f, _ in forms), forms
 
 
 def particles(pm, n, seed, dyadic=False, dev='cuda'):
@@ -65,6 +77,20 @@ MESHES = [(128, 128, 128), (64, 192, 256), (128, 64, 512), (64, 64, 1024), (64, 
 @pytest.mark.parametrize('nmesh', MESHES)
 @pytest.mark.parametrize('blocked', [False, True])
 def test_r2c_of_a_deferred_paint_equals_the_eager_one(hip, name, dtype, nmesh, blocked):
+    deferred_equals_eager(hip, name, dtype, nmesh, blocked)
+
+
+@pytest.mark.parametrize('dtype', ['f8', 'f4'])
+@pytest.mark.parametrize('nmesh', MESHES)
+@pytest.mark.parametrize('blocked', [False, True])
+def test_r2c_of_a_deferred_paint_equals_the_eager_one_blocks(hip, dtype, nmesh, blocked):
+    """the same with the plan in block-entry form (CIC, positions in doubles, the whole mesh; double and float
+    canvases): paint_entries_kernel stages the halos, the row pass of r2c gathers them"""
+    use_blocks(hip)
+    deferred_equals_eager(hip, 'cic', dtype, nmesh, blocked, blocks=True)
+
+
+def deferred_equals_eager(hip, name, dtype, nmesh, blocked, blocks=False):
     if nmesh[2] == 2048 and dtype == 'f8':
         nmesh = (64, 64, 256)       # (rows of 2048 doubles keep the merge kernel: test_rows_the_gather_is_not_built_for)
     pm = ParticleMesh(Nmesh=nmesh, BoxSize=[100.0, 75.0, 130.0], dtype=dtype, resampler=name)
@@ -79,6 +105,8 @@ def test_r2c_of_a_deferred_paint_equals_the_eager_one(hip, name, dtype, nmesh, b
     pmod.HALO_DEFER = 'fresh'
     lazy = pm.paint(pos, mass=mass)
     assert owes(lazy), 'the paint did not leave its halo merge to the transform'
+    if blocks:
+        assert_entry_form(hip)
     lk = lazy.r2c(out=Ellipsis)
     assert not owes(lazy)
     lk = lk.value
@@ -120,6 +148,24 @@ def _eager_value(pm, pos, mass):
 def test_dyadic_inputs_bit_for_bit(hip, name, nmesh):
     """exact partial sums: the spectrum of the deferred field equals the eager one bit for bit only if every staged
     halo cell was added to exactly the mesh cell the merge kernel adds it to (the row pass then sees equal rows)"""
+    dyadic_bit_for_bit(hip, name, nmesh)
+
+
+@pytest.mark.parametrize('nmesh', MESHES[:4])
+def test_dyadic_inputs_bit_for_bit_blocks(hip, oracle, nmesh):
+    """the same through the block-entry paint (paint_entries_kernel, defer = 1, then the gather of the row pass), and
+    the eager entry paint against the oracle bit for bit"""
+    use_blocks(hip)
+    ev = dyadic_bit_for_bit(hip, 'cic', nmesh, blocks=True)
+    pm = ParticleMesh(Nmesh=nmesh, BoxSize=[float(x) for x in nmesh], dtype='f8', resampler='cic')
+    pos, mass = particles(pm, int(numpy.prod(nmesh)) // 3, 5, dyadic=True)
+    want = numpy.zeros(nmesh)
+    oracle.Window(window.windows['cic'].kind).paint(want, pos.cpu().numpy(), mass=mass.cpu().numpy(),
+                                                    transform=oracle.Affine(3, period=nmesh))
+    assert_array_equal(ev, want)
+
+
+def dyadic_bit_for_bit(hip, name, nmesh, blocks=False):
     pm = ParticleMesh(Nmesh=nmesh, BoxSize=[float(x) for x in nmesh], dtype='f8', resampler=name)    # (scale 1: exact cells)
     n = int(numpy.prod(nmesh)) // 3
     pos, mass = particles(pm, n, 5, dyadic=True)
@@ -131,6 +177,8 @@ def test_dyadic_inputs_bit_for_bit(hip, name, nmesh):
     pmod.HALO_DEFER = 'fresh'
     lazy = pm.paint(pos, mass=mass)
     assert owes(lazy)
+    if blocks:
+        assert_entry_form(hip)
     lk = lazy.r2c(out=Ellipsis).value
     if name == 'cic':       # CIC weights of 1/8-cell offsets are dyadic: sums exact, spectra identical
         assert_array_equal(lk.cpu().numpy(), ek.cpu().numpy())
@@ -145,6 +193,9 @@ def test_dyadic_inputs_bit_for_bit(hip, name, nmesh):
         assert_array_equal(v.cpu().numpy(), ev.cpu().numpy())
     else:
         assert_allclose(v.cpu().numpy(), ev.cpu().numpy(), rtol=0, atol=1e-13)
+    if blocks:
+        assert_entry_form(hip)
+    return ev.cpu().numpy()
 
 
 def test_every_other_reader_pays_the_debt_first(hip):
