@@ -32,7 +32,6 @@
 // cells with l in [max(0, t*T-o), min(size, (t+1)*T-o)), everything else valid is halo.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "pmx_binplan.h"
@@ -298,10 +297,6 @@ __global__ void __launch_bounds__(TBLOCK) bin_count_kernel(pmx_painter p, BinGeo
 constexpr int BLOCK_ITERS = PMX_BLOCK_ITERS;                     // trips of TBLOCK * PMX_ONEPASS_U rows
 constexpr int BLOCK_ROWS = TBLOCK * PMX_ONEPASS_U * BLOCK_ITERS;
 constexpr int BLOCK_HT = 128;                       // entries of the LDS table (a power of two)
-#if !defined(PMX_EXPERIMENT) || !defined(PMX_EXP_BINFLOOR)
-#undef PMX_EXP_BINFLOOR
-#define PMX_EXP_BINFLOOR 0                          // timing experiment (-DPMX_EXPERIMENT builds only), see bin_block_kernel
-#endif
 // 16-byte pieces of the TBLOCK * U dense rows from `base` on, one per thread and q: -> bytes requested
 template <int NPRE, int U>
 __device__ __forceinline__ int request_rows(const DVec &pos, int64_t n, int64_t base, uint4 (&pre)[NPRE])
@@ -412,11 +407,6 @@ __global__ void __launch_bounds__(TBLOCK) bin_block_kernel(pmx_painter p, BinGeo
                 }
                 const int leader = t >= 0 ? __ffsll((long long)same) - 1 : lane;
                 uint32_t w = 0, bd = 0;
-#if PMX_EXP_BINFLOOR
-                // timing experiment (wrong lists): no table, no counters — what positions -> tile ids -> list costs
-                where[(it * U + u) * TBLOCK + threadIdx.x] = t >= 0 ? (uint32_t)(t & 0xFFFFFF) : EMPTY;
-                if (PMX_EXP_BINFLOOR > 1) continue;
-#endif
                 if (t >= 0 && lane == leader) {
                     // the group's entry of the table and its first rank there
                     uint32_t h = ((uint32_t)t * 2654435761u) >> 25;               // 7 bits: BLOCK_HT = 128
@@ -464,10 +454,6 @@ __global__ void __launch_bounds__(TBLOCK) bin_block_kernel(pmx_painter p, BinGeo
                 const uint32_t w = where[(it * U + u) * TBLOCK + threadIdx.x];
                 if (w == EMPTY) continue;
                 const int64_t i = row0 + (int64_t)it * (TBLOCK * U) + u * TBLOCK + threadIdx.x;
-#if PMX_EXP_BINFLOOR > 1
-                list[i] = (uint32_t)i + (w & 1);      // sequential: the floor of reading rows and writing a list
-                continue;
-#endif
                 const uint32_t e = w >> 24;
                 const int64_t slot = first[e] + (w & 0xFFFFFFu);
                 if (slot < last[e]) list[slot] = (uint32_t)i;
@@ -634,13 +620,6 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
             for (int u = 0; u < U; u++) {
                 const int64_t i = base + lrow(u);
                 t[u] = i < n ? row_tile<KIND, WHOLE>(p, g, row[u]) : -1;
-#if defined(PMX_EXPERIMENT) && defined(PMX_EXP_LEANBIN)
-                // timing experiments (wrong lists): 1: no match loop, no table: the list written sequentially;
-                // 2: no list either (the tile ids summed into the coherence counter); 3: the rows summed, no tile
-                if (PMX_EXP_LEANBIN == 1) { where[(it * U + u) * TBLOCK + threadIdx.x] = t[u] >= 0 ? (uint32_t)(t[u] & 1) : EMPTY; continue; }
-                if (PMX_EXP_LEANBIN == 2) { nbreaks += (uint32_t)t[u]; where[(it * U + u) * TBLOCK + threadIdx.x] = EMPTY; continue; }
-                if (PMX_EXP_LEANBIN == 3) { nbreaks += (uint32_t)(int)((double)row[u].x[0] + (double)row[u].x[1] + (double)row[u].x[2]); where[(it * U + u) * TBLOCK + threadIdx.x] = EMPTY; continue; }
-#endif
                 // the lanes that share my tile (ballots only)
                 unsigned long long sm = 0, active = __ballot(t[u] >= 0);
                 while (active) {
@@ -659,9 +638,6 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
                     nsampled += (uint32_t)__popcll(__ballot(t[u] >= 0));
                 }
             }
-#if defined(PMX_EXPERIMENT) && defined(PMX_EXP_LEANBIN)
-            continue;
-#endif
             bool lead[U];
             uint32_t h[U], k[U], e[U], w[U], bd[U];
 #pragma unroll
@@ -757,10 +733,6 @@ __device__ __forceinline__ void lean_blocks(const pmx_painter &p, const BinGeom 
                 const uint32_t w = where[(it * U + u) * TBLOCK + threadIdx.x];
                 if (w == EMPTY) continue;
                 const int64_t i = row0 + (int64_t)it * (TBLOCK * U) + lrow(u);
-#if defined(PMX_EXPERIMENT) && defined(PMX_EXP_LEANBIN)
-                list[i] = (uint32_t)i + (w & 1);
-                continue;
-#endif
                 const uint32_t e = w >> 24;
                 const int64_t slot = first[e] + (w & 0xFFFFFFu);
                 if (ENT) {
@@ -1012,7 +984,7 @@ __device__ __forceinline__ void region_tables(const pmx_painter &p, const BinGeo
 
 // per-particle setup shared by paint and readout: weights and local base of the stencil
 // all three axes are the whole periodic mesh (the one-rank case): see particle_setup
-__device__ __forceinline__ bool whole_mesh(const pmx_painter &p, const BinGeom &g)
+__host__ __device__ __forceinline__ bool whole_mesh(const pmx_painter &p, const BinGeom &g)
 {
     bool w = true;
 #pragma unroll
@@ -1083,22 +1055,8 @@ __device__ __forceinline__ void particle_setup_fast(const pmx_painter &p, const 
     }
 }
 
-// timing experiments (wrong results; -DPMX_EXPERIMENT builds only, profiled with PMESH_AMD_BENCH_NOCHECK=1, which prints no bench line): where does the deposit spend its time?
-//   PMX_EXP_NOATOM: the weights are computed and folded into one register, nothing goes to LDS
-//   PMX_EXP_NOWEIGHT: the LDS atomics with a constant instead of the weight products
-#ifndef PMX_FIXED_POINT
-#define PMX_FIXED_POINT 1
-#endif
 #ifndef PMX_FIXED_MIN_S
 #define PMX_FIXED_MIN_S 3
-#endif
-#if !defined(PMX_EXPERIMENT) || !defined(PMX_EXP_NOATOM)
-#undef PMX_EXP_NOATOM
-#define PMX_EXP_NOATOM 0
-#endif
-#if !defined(PMX_EXPERIMENT) || !defined(PMX_EXP_NOWEIGHT)
-#undef PMX_EXP_NOWEIGHT
-#define PMX_EXP_NOWEIGHT 0
 #endif
 
 // ---- fixed-point accumulation (FIXED) -------------------------------------------------------------------
@@ -1156,21 +1114,6 @@ __device__ __forceinline__ double uniform_double(double x)
 // a clustered set cost 4 instead of 14 clocks per particle, the vector work 6.2 instead of 5.0.  Same cells (the index
 // arithmetic is untouched), same fixed-point sums up to the z weight's rounding (a cubic in Horner form instead of the
 // factored one: absolute difference <= 2^-52 of the particle's mass per cell, far inside the contract's 1e-12).
-#ifndef PMX_QUAD_PCS
-#define PMX_QUAD_PCS 1
-#endif
-#ifndef PMX_DEAL_CROWDED
-#define PMX_DEAL_CROWDED 0      // (an experiment: see tile_deposit)
-#endif
-#ifndef PMX_DEAL_SAME_OF_64
-#define PMX_DEAL_SAME_OF_64 24       // neighbouring entries of the sample that share their first cell, from which on the rows count as cell-ordered
-#endif
-#ifndef PMX_DEAL_MIN_DEFAULT
-#define PMX_DEAL_MIN_DEFAULT (2 * TCELLS)
-#endif
-#ifndef PMX_QUAD_STRIDE8
-#define PMX_QUAD_STRIDE8 1
-#endif
 #ifndef PMX_QUAD_MIN_DEFAULT
 #define PMX_QUAD_MIN_DEFAULT (9 * TCELLS / 8)
 #endif
@@ -1212,16 +1155,12 @@ __device__ __forceinline__ void tile_deposit_quadz(const pmx_painter &p, const B
         double x[UNROLL][3], m[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
-#if PMX_QUAD_STRIDE8
             // a wave holds 128 CONSECUTIVE entries, the quad k of it entries 8k .. 8k + 7 (lane q: 8k + q and 8k + 4 + q):
             // the 16 particles of an instruction are then 8 entries apart — neighbouring quads' z runs of four cells
             // do not overlap up to two particles per cell (4 apart they did on a lattice of 2 per cell: 5.5 against
             // 4.4 ms), and the loads still cover whole lines
             static_assert(UNROLL == 2, "two entries per lane");
             const int j = jb + ((int)threadIdx.x >> 6) * 128 + 2 * ((int)threadIdx.x & 63) - q + 4 * u;
-#else
-            const int j = jb + u * TTHREADS + (int)threadIdx.x;
-#endif
             idx[u] = j < count ? (SORTED ? start + j : (int64_t)tl[j]) : -1;
         }
 #pragma unroll
@@ -1296,7 +1235,7 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
                                              const DVec &mass, double mass_scalar, const uint32_t *list,
                                              int64_t start, int count, double *lds, double scale = 1.0)
 {
-    if constexpr (PMX_QUAD_PCS && KIND == PMX_TUNED_PCS && FIXED && !std::is_same<WF, void>::value) {
+    if constexpr (KIND == PMX_TUNED_PCS && FIXED && !std::is_same<WF, void>::value) {
         // (uniform per workgroup: `count` is the tile's)
         if (SORTED || count >= g.quad_min) {
             tile_deposit_quadz<TTHREADS, SORTED, PE, WHOLE, WF>(p, g, t, pos, mass, mass_scalar, list, start, count, lds, scale);
@@ -1316,54 +1255,10 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
     // a 64-bit LDS atomic is served in groups of 16 consecutive lanes, two lanes of a group on one address cost 12.3
     // instead of 6.5 clocks per instruction, on one bank 8.3, lanes of different groups meet for free; the deal took the
     // benchmark's pattern from 12.1 to 8.4 clocks there — and changed nothing in this kernel: TSC f4 paint 1.65 / 1.65 ms,
-    // PCS 2.77 / 2.90, with the odd-lane swap on top 1.78 / 3.22.  The kernel is not waiting for those conflicts.)
-    double sink = 0;
+    // PCS 2.77 / 2.90, with the odd-lane swap on top 1.78 / 3.22.  The kernel is not waiting for those conflicts.
+    // [r6] Dealing only the entries of crowded tiles whose rows are sorted by cell was measured too and removed: it cost
+    // the CIC kernel 14 registers and the benchmark's paint 7-12 %)
     const uint32_t *tl = list + start;       // (a wave-uniform base + the lane's entry: nothing per thread for the compiler to keep across tiles)
-#if PMX_DEAL_CROWDED
-    // [r6] (experiment builds only, -DPMX_DEAL_CROWDED=1) Crowded tiles deal their entries: slot s of a trip of W takes
-    // entry (65 s) mod W.  Rows that arrive sorted by cell — a caller that keeps its particles in Peano-Hilbert or cell
-    // order, as tree codes do — put the particles of a crowded cell into neighbouring lanes, every lane of an instruction
-    // on ONE address: an evolved 512^3 state (scripts/clustered_state_probe.py) painted in 4.2 ms cell-sorted against 1.4
-    // in random order, 2.2 with the deal.  Whether a crowded tile's rows ARE in cell order is looked up on 64 entries from
-    // the middle of its list (rows that merely arrive in the order the particles were made in lose the locality of
-    // their gathers for nothing when dealt: 2.30 -> 3.18 ms).  NOT in the product: the sample and the slots cost the CIC
-    // kernel 14 registers — 69 instead of 55, the fourth workgroup of a CU — and the benchmark's paint 7-12 %
-    // (scripts/r06/deal_ab.sh); pm.tile_order, which sorts by tile and NOT by cell, is the remedy a caller has.
-    constexpr int W = TTHREADS * UNROLL;
-    constexpr bool CAN_DEAL = !FIXED && !sorted && !ENT && (W & (W - 1)) == 0;
-    bool deal = false;
-    if (CAN_DEAL && count >= g.deal_min) {      // (uniform per workgroup)
-        __shared__ int deal_flag;
-        if (threadIdx.x < 64) {
-            const int64_t row = (int64_t)tl[count / 2 + (int)threadIdx.x];
-            int key = 0;
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const double X = (double)pos_get<PE>(pos, row, d) * p.scale[d] + p.translate[d];
-                key = key * 1021 + Tuned<KIND>::first(X);
-            }
-            const int prev = __shfl_up(key, 1);
-            const unsigned long long same = __ballot(threadIdx.x > 0 && key == prev);
-            if (threadIdx.x == 0) deal_flag = __popcll(same) >= PMX_DEAL_SAME_OF_64;
-        }
-        __syncthreads();
-        deal = deal_flag != 0;
-    }
-    int slot[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; u++) {
-        const int s = u * TTHREADS + (int)threadIdx.x;
-        slot[u] = (CAN_DEAL && deal) ? ((s * 65) & (W - 1)) : s;
-    }
-    for (int j0 = 0; j0 < count; j0 += W) {
-        int64_t idx[UNROLL];
-        double x[UNROLL][3], m[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-            const int j = j0 + slot[u];
-            idx[u] = j < count ? (sorted ? start + j : (int64_t)tl[j]) : -1;
-        }
-#else
     for (int j0 = threadIdx.x; j0 < count; j0 += TTHREADS * UNROLL) {
         int64_t idx[UNROLL];
         double x[UNROLL][3], m[UNROLL];
@@ -1374,9 +1269,8 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
                 const uint2 e = j < count ? ((const uint2 *)list)[start + (j >> 5)] : make_uint2(0u, 0u);
                 idx[u] = ((e.y >> (j & 31)) & 1u) ? (int64_t)e.x * 32 + (j & 31) : -1;
             } else
-            idx[u] = j < count ? (sorted ? start + j : (int64_t)tl[j]) : -1;
+                idx[u] = j < count ? (sorted ? start + j : (int64_t)tl[j]) : -1;
         }
-#endif
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             if (idx[u] >= 0) {
@@ -1440,9 +1334,7 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
 #pragma unroll
                     for (int c = 0; c < S; c++) {
                         const int cell = (inhalo[c] ? ihalo : imain) + c;
-                        if (PMX_EXP_NOATOM) sink += fb * V[2][c];
-                        else if (PMX_EXP_NOWEIGHT) unsafeAtomicAdd(&lds[cell], m[u]);
-                        else if (FIXED) {
+                        if (FIXED) {
                             const double r = __builtin_fma(fb, V[2][c], FIXED_MAGIC);
                             atomicAdd((unsigned long long *)&lds[cell],
                                       (unsigned long long)(__double_as_longlong(r) - FIXED_MAGIC_BITS));
@@ -1451,7 +1343,6 @@ __device__ __forceinline__ void tile_deposit(const pmx_painter &p, const BinGeom
                 }
         }
     }
-    if (PMX_EXP_NOATOM && sink == 12345.678) lds[0] = sink;
 }
 
 // (the form of the loop chosen once per launch: see tile_gather_any)
@@ -1572,18 +1463,15 @@ __device__ __forceinline__ void tile_gather_any(bool whole, const pmx_painter &p
 // Measured (same box, off / on): PCS paint 2.76 -> 2.60 ms, clustered 3.55 -> 3.38; TSC paint 1.62 -> 1.65, CIC the
 // same; the readouts LOSE (one more live register: PCS on 768 threads 1.68 -> 2.46 ms, TSC f4 1.08 -> 1.16): on for
 // PCS paint only.
-#ifndef PMX_LIST_PREFETCH
-#define PMX_LIST_PREFETCH 1
-#endif
 __device__ __forceinline__ uint32_t list_touch(const uint32_t *list, int64_t start, int count)
 {
     uint32_t v = 0;
-    if (PMX_LIST_PREFETCH && (int)threadIdx.x * 32 < count) v = list[start + (int)threadIdx.x * 32];
+    if ((int)threadIdx.x * 32 < count) v = list[start + (int)threadIdx.x * 32];
     return v;
 }
 __device__ __forceinline__ void list_touch_done(uint32_t v)
 {
-    if (PMX_LIST_PREFETCH) asm volatile("" ::"v"(v));
+    asm volatile("" ::"v"(v));
 }
 
 // Threads of a tile workgroup.  The LDS region fixes the workgroups per CU (4 / 3 / 2 for CIC /
@@ -1633,11 +1521,8 @@ __device__ __forceinline__ bool batch_is_mine(const double *mstats, int want_odd
 
 // which weights the deposit of a paint kernel forms: the RELAXED ones in the canvas' precision for the fixed-point
 // regions of the S >= 3 windows (MODE 1), the reference's for everything else (see tile_deposit)
-#ifndef PMX_FAST_DEPOSIT
-#define PMX_FAST_DEPOSIT 1
-#endif
 template <int KIND, typename T, int MODE> struct DepositWeights {
-    using type = typename std::conditional<(PMX_FAST_DEPOSIT && MODE == 1 && Tuned<KIND>::S >= 3), T, void>::type;
+    using type = typename std::conditional<(MODE == 1 && Tuned<KIND>::S >= 3), T, void>::type;
 };
 
 // waves per SIMD the compiler must leave room for (the register budget): the regions allow 4 / 3 / 2 workgroups of
@@ -1876,9 +1761,6 @@ __global__ void __launch_bounds__(TTHREADS, (paint_min_waves<KIND, false, MODE>(
 // (absolute error 2^-f-1), the region's sum is exact in integers, the float canvas gets it rounded once more (twice
 // for a tile in two parts): inside |d| <= 2e-6 max(1, max |cell|), the tolerance of a float canvas.
 // The face carried from tile to tile of a segment is kept in 64 bits: a tile in two parts hands on more than 32.
-#ifndef PMX_REGION32
-#define PMX_REGION32 1
-#endif
 #ifndef PMX_PITCH32_TSC
 #define PMX_PITCH32_TSC 64
 #endif
@@ -1942,10 +1824,7 @@ __device__ __forceinline__ uint32_t tile_deposit32(const pmx_painter &p, const B
     constexpr int S = Tuned<KIND>::S;
     using Rg = Region<S>;
     constexpr int R1 = Rg::R1, P = Tile32<KIND>::P;
-#ifndef PMX_SWAP32
-#define PMX_SWAP32 1
-#endif
-    constexpr bool SWAP = PMX_SWAP32 && UNROLL == 2;
+    constexpr bool SWAP = UNROLL == 2;
     // stencil points in groups of G atomics; the values a group returns are folded into the guard behind the NEXT
     // group's atomics: G registers of returns in flight instead of S^3 (left alone the compiler issues all S^3 first)
     constexpr int G = S == 3 ? 9 : 8, NG = S * S * S / G;
@@ -2187,11 +2066,7 @@ __global__ void __launch_bounds__(TTHREADS, (Tile32<KIND>::waves)) paint_tile32_
         if (!two) {
             zero_region();
             place_carry(0, 0);
-#if defined(PMX_EXPERIMENT) && defined(PMX_EXP_NODEPOSIT32)
-            const uint32_t over = 0;        // timing experiment: everything but the deposit loop
-#else
             const uint32_t over = tile_deposit32<KIND, TTHREADS, SORTED, PE, WHOLE, SIGNED, 0>(p, g, t, pos, mass, mass_scalar, list, start, count, lds, pow2(f));
-#endif
             two = overflowed(over);
             if (!two) {
                 flush(pow2(-f), false);
@@ -2412,16 +2287,13 @@ __device__ __forceinline__ void tile_gather_lean(const pmx_painter &p, const Bin
 // (768 threads — PCS on double canvases, an 81 KB region: TWO workgroups per CU need 6 waves per SIMD, i.e. at most 80
 // VGPRs.  The form for blocks of any shape came to 83 and ran ONE: 2.62 ms against 1.75 at 512^3 — every pencil rank
 // of config 5 runs that form.  The bound makes the compiler hold it.)
-// [r6] PMX_READOUT_XCD: tiles in XCD order (xcd_tile): the z- and y-neighbours of a tile, which fetch the face lines of
+// [r6] PCS (S >= 4): tiles in XCD order (xcd_tile): the z- and y-neighbours of a tile, which fetch the face lines of
 // its region as rows of their own, run at the same time on the same L2.  Measured between two builds of this file that
 // differ in nothing else (scripts/r06/lib_ab2.sh, profiles/r06_rxcd/): PCS gains (512^3 1.75-1.77 -> 1.66-1.69 ms,
 // config 5's per-GPU load 33.1-33.4 -> 32.5-32.6: its region is 11 x 19 x 35 cells for a box of 8 x 16 x 32, the faces are
 // half of what it fetches), CIC and TSC LOSE (1.12-1.16 -> 1.19-1.24, 1.46 -> 1.49-1.50; rows that have drifted 4 cells
 // 2.03 -> 2.63): eight far-apart streams through the particle rows, which are most of their traffic, instead of one.
-// 1 (default): PCS only; 2: every window (the measurement build); 0: none.
-#ifndef PMX_READOUT_XCD
-#define PMX_READOUT_XCD 1
-#endif
+// (The build that put every window in XCD order was removed.)
 // (the body of readout_tile_lean_kernel and, ENT: `list` holds block entries, readout_entries_kernel)
 template <int KIND, typename T, int TTHREADS, int PE, int OE, bool WHOLE, bool ENT>
 __device__ __forceinline__ void readout_lean_body(const pmx_painter &p, const BinGeom &g, const char *canvas,
@@ -2453,7 +2325,7 @@ __device__ __forceinline__ void readout_lean_body(const pmx_painter &p, const Bi
     const int64_t nh = *nitems < cap ? *nitems : cap;
     for (int64_t unit = blockIdx.x; unit < g.ntiles + nh; unit += gridDim.x) {
         int64_t tile = unit, first = 0;
-        if ((PMX_READOUT_XCD >= 2 || (PMX_READOUT_XCD == 1 && S >= 4)) && unit < g.ntiles) tile = xcd_tile(unit, g.ntiles);
+        if (S >= 4 && unit < g.ntiles) tile = xcd_tile(unit, g.ntiles);
         if (unit >= g.ntiles) {
             const uint64_t it = items[unit - g.ntiles];
             tile = (int64_t)(it >> 20);
@@ -2534,7 +2406,7 @@ __global__ void __launch_bounds__(TTHREADS, (TTHREADS == 768 ? PMX_READOUT768_WA
     const int64_t nh = *nitems < cap ? *nitems : cap;
     for (int64_t unit = blockIdx.x; unit < g.ntiles + nh; unit += gridDim.x) {
         int64_t tile = unit, first = 0;
-        if ((PMX_READOUT_XCD >= 2 || (PMX_READOUT_XCD == 1 && S >= 4)) && unit < g.ntiles) tile = xcd_tile(unit, g.ntiles);
+        if (S >= 4 && unit < g.ntiles) tile = xcd_tile(unit, g.ntiles);
         if (unit >= g.ntiles) {
             const uint64_t it = items[unit - g.ntiles];
             tile = (int64_t)(it >> 20);
@@ -2789,6 +2661,40 @@ static int halo_cells(int S)
     return R0 * R1 * R2 - TCELLS;
 }
 
+// workgroups of a launch over n units (the kernels loop over what is left)
+static unsigned grid_cap(int64_t n) { return (unsigned)(n < 65535 * 8 ? n : 65535 * 8); }
+
+// ---- launch dispatch: a runtime value becomes a compile-time tag, handed to a generic lambda --------------------------
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename T> struct type_c { using type = T; };
+// the window kind (anything that is not NNB, CIC or TSC is PCS)
+template <typename F> void with_kind(int kind, F &&f)
+{
+    switch (kind) {
+    case PMX_TUNED_NNB: f(int_c<PMX_TUNED_NNB>{}); break;
+    case PMX_TUNED_CIC: f(int_c<PMX_TUNED_CIC>{}); break;
+    case PMX_TUNED_TSC: f(int_c<PMX_TUNED_TSC>{}); break;
+    default: f(int_c<PMX_TUNED_PCS>{}); break;
+    }
+}
+template <typename F> void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// an element size of 8 or 4 bytes (positions, results)
+template <typename F> void with_elsize(int elsize, F &&f)
+{
+    if (elsize == 8) f(int_c<8>{});
+    else f(int_c<4>{});
+}
+// the canvas type from its element size
+template <typename F> void with_canvas(int elsize, F &&f)
+{
+    if (elsize == 8) f(type_c<double>{});
+    else f(type_c<float>{});
+}
+
 }  // namespace pmx
 
 using namespace pmx;
@@ -2973,7 +2879,7 @@ extern "C" int pmx_binplan_order(pmx_binplan *pl, int64_t *order, void *stream)
     int64_t *first = nullptr;
     PMX_HIP_CHECK(hipMallocAsync((void **)&first, (size_t)nbuckets * sizeof(int64_t), st));
     order_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, nbuckets, first);
-    const unsigned grid = (unsigned)(nbuckets < 65535 * 8 ? nbuckets : 65535 * 8);
+    const unsigned grid = grid_cap(nbuckets);
     order_copy_kernel<<<grid, TBLOCK, 0, st>>>(pl->list, pl->offsets, pl->counts, first, nbuckets, order);
     hipError_t e = hipGetLastError();
     (void)hipFreeAsync(first, st);
@@ -3077,13 +2983,8 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // 2.30 / 2.58 (its lanes rarely meet; the quad form's extra vector work shows) and steps of 4 cells 2.74 / 2.78:
         // tiles at the mean density of a uniform set keep the lane-per-particle loop.  (A criterion from the row order
         // the bin pass measures was tried first: a clustered set displaces neighbours together — 4 changes of tile per
-        // 64 rows, like a lattice — and does not stand out there.)  PMX_QUAD_MIN: experiments.
-        static const int quad_min = [] { const char *e = getenv("PMX_QUAD_MIN"); return e ? atoi(e) : (int)(PMX_QUAD_MIN_DEFAULT); }();
-        g.quad_min = quad_min;
-        // [r6] ... and which tiles of the one-lane loops deal their entries to the lanes (tile_deposit): from two particles
-        // per cell on (PMX_DEAL_MIN: experiments)
-        static const int deal_min = [] { const char *e = getenv("PMX_DEAL_MIN"); return e ? atoi(e) : (int)(PMX_DEAL_MIN_DEFAULT); }();
-        g.deal_min = deal_min;
+        // 64 rows, like a lattice — and does not stand out there.)
+        g.quad_min = PMX_QUAD_MIN_DEFAULT;
     }
     g.chunk = 1 << 30;
     {
@@ -3130,9 +3031,8 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
             pl->skip = pl->distrust;
             // [r6] ... and the ranges of the builds that follow carry more slack (slot_capacity).  (The back-off above is a
             // host-side hint: a caller that runs ten steps ahead of the device sees the flag ten steps late and the
-            // distrust never builds up; the slack, raised once, stays.)  PMX_SLACK_ADAPT=0: the fixed quarter.
-            static const bool adapt = [] { const char *e = getenv("PMX_SLACK_ADAPT"); return !(e && atoi(e) == 0); }();
-            if (adapt && pl->slack < 2) pl->slack++;
+            // distrust never builds up; the slack, raised once, stays.)
+            if (pl->slack < 2) pl->slack++;
         } else if (pl->last_reuse && pl->distrust > 0) {
             // the previous single-pass build raised no flag (as far as the host has seen): trust returns
             // step by step, so that one overflow late in a long run does not cost 64 two-pass builds
@@ -3206,31 +3106,21 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // contiguous (n, 3) rows on a 16-byte boundary take the dense staging path
         const bool dense = pos->stride1 == pos->elsize && pos->stride0 == 3 * (int64_t)pos->elsize &&
                            (((uintptr_t)pos->data) & 15) == 0;
-#define BC2(K, MODE, GRID, GATE, SP)                                                                              \
-    do {                                                                                                        \
-        if (dense) bin_count_kernel<K, true, MODE, SP><<<GRID, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->tid, pl->counts, \
-                pl->flags, pl->offsets, pl->list, pl->host_flag, GATE, inv, copyp, pl->cursor);                 \
-        else bin_count_kernel<K, false, MODE, SP><<<GRID, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->tid, pl->counts,  \
-                pl->flags, pl->offsets, pl->list, pl->host_flag, GATE, inv, copyp, pl->cursor);                 \
-    } while (0)
-#define BC(K, MODE, GRID, GATE)                                                                                 \
-    do {                                                                                                        \
-        if (inv != nullptr) BC2(K, MODE, GRID, GATE, true);                                                     \
-        else BC2(K, MODE, GRID, GATE, false);                                                                   \
-    } while (0)
-#define BCK(MODE, GRID, GATE)                                                                                   \
-    do {                                                                                                        \
-        switch (p.kind) {                                                                                       \
-        case PMX_TUNED_NNB: BC(PMX_TUNED_NNB, MODE, GRID, GATE); break;                                         \
-        case PMX_TUNED_CIC: BC(PMX_TUNED_CIC, MODE, GRID, GATE); break;                                         \
-        case PMX_TUNED_TSC: BC(PMX_TUNED_TSC, MODE, GRID, GATE); break;                                         \
-        default: BC(PMX_TUNED_PCS, MODE, GRID, GATE); break;                                                    \
-        }                                                                                                       \
-    } while (0)
         const uint32_t *nogate = nullptr;
         uint32_t *inv = nullptr;
         void *copyp = nullptr;               // != NULL: the single-pass rebuild writes the tile-ordered copy itself
         const uint32_t *copy_gate = nullptr; // the gather of the copy then only runs after an overflow repair
+        // the per-wave pass (bin_count_kernel) in MODE 0 / 1 / 3
+        auto count_pass = [&](auto mode, unsigned grid, const uint32_t *gate) {
+            with_kind(p.kind, [&](auto k) {
+                with_bool(dense, [&](auto dn) {
+                    with_bool(inv != nullptr, [&](auto sp) {
+                        bin_count_kernel<k, dn, mode, sp><<<grid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->tid, pl->counts, pl->flags, pl->offsets,
+                                                                                 pl->list, pl->host_flag, gate, inv, copyp, pl->cursor);
+                    });
+                });
+            });
+        };
         if (!pl->host_groups) {
             PMX_HIP_CHECK(hipHostMalloc((void **)&pl->host_groups, 64, hipHostMallocDefault));
             pl->host_groups[0] = 0;                 // breaks of the tile sequence among ...
@@ -3248,9 +3138,6 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // 9.50 against 7.06 / 7.67 / 10.58 / 11.04; only rows in no order at all (63) gain: 22.8 against 14.4.
         // Two thresholds: a plan takes the copy above 61.5 and gives it up below 58 (position sets on either side of ONE
         // threshold made the plan start over every step: 11.1 ms at 8 cells of jitter against 9.5 in either form).
-#ifndef PMX_LEAN_BIN
-#define PMX_LEAN_BIN 1
-#endif
 #ifndef PMX_BLOCKS_TAKE_BREAKS
 #define PMX_BLOCKS_TAKE_BREAKS 6.0
 #endif
@@ -3263,12 +3150,10 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // at most PMX_BLOCKS_TAKE_BREAKS breaks of the tile sequence per 64 rows and gives them up above
         // PMX_BLOCKS_DROP_BREAKS (two thresholds, as for the copy); a crowded tile seen by the last build keeps the list
         // (its pieces are split over workgroups; a tile in entry form is one workgroup's).
-        bool whole_p = true;
-        for (int d = 0; d < 3; d++) whole_p = whole_p && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];
         // (sticky: a plan that has seen a crowded tile, or has given the entries up twice — position sets that alternate
         // between orders — keeps the list for good rather than paying a two-pass build at every change of form)
         const bool crowded = *(volatile uint32_t *)(pl->host_flag + 4) != 0 || pl->blocks_drops >= 2;
-        const bool blocks_ok = PMX_LEAN_BIN && dense && whole_p && pos->elsize == 8 && p.kind == PMX_TUNED_CIC && pl->form != 2 &&
+        const bool blocks_ok = dense && whole_mesh(p, g) && pos->elsize == 8 && p.kind == PMX_TUNED_CIC && pl->form != 2 &&
                                pl->sort_pref != 1 && !pl->deterministic && !pl->blocks_off && npart < ((int64_t)1 << 32);
         bool blocks_now = false;
         if (blocks_ok) {
@@ -3297,31 +3182,22 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         // the block form of the pass (bin_lean_kernel for dense rows, else bin_block_kernel): into the ranges `offsets`
         // names — or, list_arg == NULL (lean form only), the counts alone
         auto block_pass = [&](uint32_t *list_arg, const uint32_t *repair_gate = nullptr) {
-            const int64_t nblocks = (npart + BLOCK_ROWS - 1) / BLOCK_ROWS;
-            const unsigned bgrid = (unsigned)(nblocks < 65535 * 8 ? nblocks : 65535 * 8);
-            bool whole_b = true;
-            for (int d = 0; d < 3; d++) whole_b = whole_b && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];      // (whole_mesh())
-#ifdef PMX_GENERAL_FORMS_ONLY
-            whole_b = false;       // (a build switch for measurements, right results: what the forms for blocks of any shape cost on a whole mesh)
-#endif
-#define BL(K, PE_, WH) do { if (repair_gate) bin_repair_lean_kernel<K, PE_, WH><<<(bgrid < PMX_REPAIR_GRID ? bgrid : PMX_REPAIR_GRID), TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, pl->cursor, list_arg, pl->host_flag, repair_gate); \
-                             else bin_lean_kernel<K, PE_, WH><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, list_arg, pl->host_flag); } while (0)
-#define BB(K)                                                                                                   \
-    do {                                                                                                        \
-        if (dense && PMX_LEAN_BIN) {                                                                            \
-            if (whole_b) { if (dpos.elsize == 8) BL(K, 8, true); else BL(K, 4, true); }                         \
-            else { if (dpos.elsize == 8) BL(K, 8, false); else BL(K, 4, false); }                               \
-        } else if (dense) bin_block_kernel<K, true><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, list_arg, pl->host_flag); \
-        else bin_block_kernel<K, false><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, list_arg, pl->host_flag); \
-    } while (0)
-            switch (p.kind) {
-            case PMX_TUNED_NNB: BB(PMX_TUNED_NNB); break;
-            case PMX_TUNED_CIC: BB(PMX_TUNED_CIC); break;
-            case PMX_TUNED_TSC: BB(PMX_TUNED_TSC); break;
-            default: BB(PMX_TUNED_PCS); break;
-            }
-#undef BB
-#undef BL
+            const unsigned bgrid = grid_cap((npart + BLOCK_ROWS - 1) / BLOCK_ROWS);
+            // (dense rows take the lean pass; bin_block_kernel's dense form is still instantiated, though not launched)
+            with_kind(p.kind, [&](auto k) {
+                with_bool(dense, [&](auto dn) {
+                    if (dense) {
+                        with_elsize(dpos.elsize, [&](auto pe) {
+                            with_bool(whole_mesh(p, g), [&](auto wh) {
+                                if (repair_gate)
+                                    bin_repair_lean_kernel<k, pe, wh><<<(bgrid < PMX_REPAIR_GRID ? bgrid : PMX_REPAIR_GRID), TBLOCK, 0, st>>>(
+                                        p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, pl->cursor, list_arg, pl->host_flag, repair_gate);
+                                else bin_lean_kernel<k, pe, wh><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, list_arg, pl->host_flag);
+                            });
+                        });
+                    } else bin_block_kernel<k, dn><<<bgrid, TBLOCK, 0, st>>>(p, g, dpos, npart, pl->counts, pl->flags, pl->offsets, list_arg, pl->host_flag);
+                });
+            });
         };
         pl->last_reuse = reuse;
         pl->builds[reuse ? 0 : 1]++;
@@ -3329,8 +3205,7 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
         if (blocks_now) {
             // [r7] block entries: one pass that emits an entry per (32-row block, tile); the gated repair is the same
             // pass into ranges laid out from the exact counts (every pass adds to a counter before it looks at the range)
-            const int64_t nblocks = (npart + BLOCK_ROWS - 1) / BLOCK_ROWS;
-            const unsigned bgrid = (unsigned)(nblocks < 65535 * 8 ? nblocks : 65535 * 8);
+            const unsigned bgrid = grid_cap((npart + BLOCK_ROWS - 1) / BLOCK_ROWS);
             const unsigned rgrid = bgrid < PMX_REPAIR_GRID ? bgrid : PMX_REPAIR_GRID;
             uint2 *ents = (uint2 *)pl->ents;
             if (reuse) {
@@ -3356,16 +3231,16 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
                 // rows in a coherent order, no tile-ordered copy: one request per tile and block of rows
                 block_pass(pl->list);
             } else
-                BCK(1, grid_for((npart + PMX_ONEPASS_U - 1) / PMX_ONEPASS_U, TBLOCK), nogate);
+                count_pass(int_c<1>{}, grid_for((npart + PMX_ONEPASS_U - 1) / PMX_ONEPASS_U, TBLOCK), nogate);
             // the repair, one launch that returns at once unless a tile overflowed (measured: the four gated launches
             // it replaces, zero / count / scan / scatter, cost a slab rank 20 us per build)
             const uint32_t *gate = pl->flags;
             // ([r6] two launches, both returning at once unless a tile overflowed: the scan of the exact counts into
             // new ranges as a workgroup of its own — the stream orders it before the fill; no workgroup waits for another)
-            const bool lean_repair = inv == nullptr && pl->form != 2 && dense && PMX_LEAN_BIN && PMX_REPAIR_GRID > 0;
+            const bool lean_repair = inv == nullptr && pl->form != 2 && dense && PMX_REPAIR_GRID > 0;
             bin_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, g.ntiles + 1, pl->offsets, pl->cursor, gate, lean_repair ? pl->counts : nullptr, pl->slack);
             if (lean_repair) block_pass(pl->list, gate);
-            else BCK(3, small_grid, gate);
+            else count_pass(int_c<3>{}, small_grid, gate);
         } else {
             // [r5] Dense rows count through the block form too (list == NULL: counts only) and fill their ranges with
             // the same pass a rebuild uses, instead of one device atomic per wave and tile in both passes: nothing
@@ -3373,12 +3248,9 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
             // the crowded tiles — 18.6 + 19.6 ms for the 2.7e8 rows of a config-5 rank against 1.1 ms per block pass.
             // (Rows in no order, which get the tile-ordered copy, need a tile id per row and the inverse list: they
             // are counted again by the per-wave kernel below.)
-#ifndef PMX_LEAN_TWOPASS
-#define PMX_LEAN_TWOPASS 1
-#endif
-            const bool lean2 = PMX_LEAN_TWOPASS && dense && PMX_LEAN_BIN && pl->form != 2 && pl->sort_pref != 1;
+            const bool lean2 = dense && pl->form != 2 && pl->sort_pref != 1;
             if (lean2) block_pass(nullptr);
-            else BCK(0, full_grid, nogate);
+            else count_pass(int_c<0>{}, full_grid, nogate);
             // How coherent is the row order?  Every build leaves its measurement in host_groups
             // (asynchronous copy, below); a two-pass build of about as many rows as that one (within an
             // eighth: ghost batches change their size from step to step, overflow repairs, reallocations)
@@ -3413,15 +3285,12 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
             } else {
                 if (lean2) {
                     PMX_HIP_CHECK(hipMemsetAsync(pl->counts, 0, (size_t)nbuckets * 4, st));
-                    BCK(0, full_grid, nogate);
+                    count_pass(int_c<0>{}, full_grid, nogate);
                 }
                 bin_scan_kernel<<<1, 1024, 0, st>>>(pl->counts, nbuckets, pl->offsets, pl->cursor, nogate, nullptr, pl->slack);
                 bin_scatter_kernel<<<full_grid, TBLOCK, 0, st>>>(pl->tid, pl->cursor, npart, pl->list, nogate, inv);
             }
         }
-#undef BCK
-#undef BC
-#undef BC2
         if (pl->sort_pref < 0 && npart >= (1 << 16)) {
             // what this build saw of the row order, read by the NEXT build (stale at worst: a hint); the build's last
             // kernel stores it into the mapped slot
@@ -3430,7 +3299,7 @@ extern "C" int pmx_binplan_build(pmx_binplan *pl, const pmx_painter *p_, const p
             pl->have_measure = true;
         }
         if (pl->sorted) {
-            const unsigned cgrid = (unsigned)(nbuckets < 65535 * 8 ? nbuckets : 65535 * 8);
+            const unsigned cgrid = grid_cap(nbuckets);
             if (pos->elsize == 8)
                 sort_copy_kernel<6><<<cgrid, TBLOCK, 0, st>>>(pl->list, pl->offsets, pl->counts, nbuckets, dpos, (uint32_t *)pl->pos_copy, copy_gate);
             else
@@ -3469,10 +3338,10 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
     size_t need = (size_t)g.ntiles * (size_t)halo_cells(g.S) * sizeof(T);
     int rc = plan_ensure(&pl->halo, &pl->cap_halo, need > 0 ? need : 16);
     if (rc) return rc;
-    unsigned grid = (unsigned)(g.ntiles < 65535 * 8 ? g.ntiles : 65535 * 8);
+    const unsigned grid = grid_cap(g.ntiles);
     const int ntw = walk_x(g.S) ? g.nt[0] : g.nt[2];
     const int64_t nwork = (g.ntiles / ntw) * ((ntw + ZSEG - 1) / ZSEG);   // segments of tiles along the walk axis
-    unsigned pgrid = (unsigned)(nwork < 65535 * 8 ? nwork : 65535 * 8);
+    const unsigned pgrid = grid_cap(nwork);
     T *halo = (T *)pl->halo;
     const bool dense_rows = pos.stride1 == pos.elsize && pos.stride0 == 3 * pos.elsize;
     if (pl->blocks && (pl->deterministic || pos.elsize != 8 || !dense_rows)) {
@@ -3495,7 +3364,7 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
     // floating-point kernels, launched behind the fixed-point ones (each returns at once when the batch is not
     // its own).  A scalar mass decides on the host.
     const bool det = pl->deterministic != 0;
-    const bool fixed_kind = det || (PMX_FIXED_POINT && g.S >= PMX_FIXED_MIN_S);
+    const bool fixed_kind = det || g.S >= PMX_FIXED_MIN_S;
     const double *mstats = nullptr;
     bool run_fixed = fixed_kind, run_float = !fixed_kind;
     if (fixed_kind) {
@@ -3532,67 +3401,80 @@ int paint_binned_t(pmx_binplan *pl, const pmx_painter &p, void *canvas, DVec pos
         pd.strides[2] = 8; pd.strides[1] = 8 * p.size[2]; pd.strides[0] = 8 * p.size[2] * p.size[1];
         det_scale_kernel<<<1, 1024, 0, st>>>(p, pl->counts, g.ntiles, mstats, ms, dexp);
     }
-#define PT3L(K, TT, MD, ODD, PP, CV, HL, OW, SD, WH, PE_) paint_tile_kernel<K, TT, TileThreads<K, TT>::paint, SD, MD, WH, PE_><<<pgrid, TileThreads<K, TT>::paint, 0, st>>>(PP, g, (char *)(CV), pos, mass, ms, pl->list, pl->offsets, pl->counts, HL, OW, mstats, ODD, dexp, p)
-#define PT3P(K, TT, MD, ODD, PP, CV, HL, OW, SD, WH) do { if (pos.elsize == 8) PT3L(K, TT, MD, ODD, PP, CV, HL, OW, SD, WH, 8); else PT3L(K, TT, MD, ODD, PP, CV, HL, OW, SD, WH, 4); } while (0)
-#define PT3W(K, TT, MD, ODD, PP, CV, HL, OW, SD) do { if (whole32) PT3P(K, TT, MD, ODD, PP, CV, HL, OW, SD, true); else PT3P(K, TT, MD, ODD, PP, CV, HL, OW, SD, false); } while (0)
-#define PT3(K, TT, MD, ODD, PP, CV, HL, OW) do { if (sorted) PT3W(K, TT, MD, ODD, PP, CV, HL, OW, true); else PT3W(K, TT, MD, ODD, PP, CV, HL, OW, false); } while (0)
     // [r5] float canvases, S >= 3: the 32-bit region (paint_tile32_kernel); contributions of either sign need its SIGNED guard
     const bool signed32 = mass.data != nullptr || ms < 0 || p.order[0] != 0 || p.order[1] != 0 || p.order[2] != 0;
     const bool dense32 = pos.stride1 == pos.elsize && pos.stride0 == 3 * pos.elsize;      // (always so for the plan's sorted copy)
-    bool whole32 = true;
-    for (int d = 0; d < 3; d++) whole32 = whole32 && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];      // (whole_mesh())
-#ifdef PMX_GENERAL_FORMS_ONLY
-    whole32 = false;       // (a build switch for measurements, right results: what the forms for blocks of any shape cost on a whole mesh)
-#endif
-#define PT32L(K, SD, SG, WH, PE_) paint_tile32_kernel<K, Tile32<K>::threads, SD, SG, WH, PE_><<<pgrid, Tile32<K>::threads, 0, st>>>(p, g, (char *)canvas, pos, mass, ms, pl->list, pl->offsets, pl->counts, (float *)halo, overwrite, mstats, 0)
-#define PT32P(K, SD, SG, WH) do { if (!dense32) { if constexpr (!SD) PT32L(K, false, SG, WH, 0); } else if (pos.elsize == 8) PT32L(K, SD, SG, WH, 8); else PT32L(K, SD, SG, WH, 4); } while (0)
-#define PT32W(K, SD, SG) do { if (whole32) PT32P(K, SD, SG, true); else PT32P(K, SD, SG, false); } while (0)
-#define PT32(K, SG) do { if (sorted) PT32W(K, true, SG); else PT32W(K, false, SG); } while (0)
-#define PT(K) do { if (run_fixed && det) PT3(K, double, 2, 0, pd, pl->dscratch, dhalo, 1); \
-                   else if (run_fixed) { if constexpr (PMX_REGION32 && std::is_same<T, float>::value && Tuned<K>::S >= 3) { if (signed32) PT32(K, true); else PT32(K, false); } \
-                                         else PT3(K, T, 1, 0, p, canvas, halo, overwrite); } \
-                   if (run_float) PT3(K, T, 0, (run_fixed ? 1 : 0), p, canvas, halo, overwrite); } while (0)
-    // (a batch is served either by the fixed-point or by the floating-point kernels: the merge of the other
-    // finds only zeros in its staging buffer... the deterministic one has a staging buffer of its own)
-#define HM(S_) do { if (defer) break; if (run_fixed && det) { halo_merge_kernel<S_, double, true><<<grid, TBLOCK, 0, st>>>(pd, g, (char *)pl->dscratch, dhalo, pl->counts, 1, mstats, 0); \
-                                            if (run_float) halo_merge_kernel<S_, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, halo, pl->counts, overwrite, mstats, 1); } \
-                    else halo_merge_kernel<S_, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, halo, pl->counts, overwrite); } while (0)
-    switch (p.kind) {
-    case PMX_TUNED_NNB: PT(PMX_TUNED_NNB); break;
-    case PMX_TUNED_CIC:
-        if (ents) paint_entries_kernel<PMX_TUNED_CIC, T, TileThreads<PMX_TUNED_CIC, T>::paint, 0, true, 8><<<pgrid, TileThreads<PMX_TUNED_CIC, T>::paint, 0, st>>>(
-                      p, g, (char *)canvas, pos, mass, ms, (const uint2 *)pl->ents, pl->offsets, pl->counts, halo, overwrite, mstats, 0, dexp, p);
-        else PT(PMX_TUNED_CIC);
-        HM(2);
-        break;
-    case PMX_TUNED_TSC: PT(PMX_TUNED_TSC); HM(3); break;
-    default: PT(PMX_TUNED_PCS); HM(4); break;
-    }
-#undef PT
-#undef PT3
-#undef PT3W
-#undef PT3P
-#undef PT3L
-#undef PT32
-#undef PT32W
-#undef PT32P
-#undef PT32L
-#undef HM
+    const bool whole = whole_mesh(p, g);
+    // the kernels of one form of the paint: canvas type tt, MD (0 floating point, 1 fixed point, 2 deterministic), odd
+    // (run behind the fixed-point kernels: see paint_tile_kernel), and where they paint to
+    auto tiles = [&](auto k, auto tt, auto md, int odd, const pmx_painter &pp, void *cv, auto *hl, int ow) {
+        using TT = typename decltype(tt)::type;
+        constexpr int TH = TileThreads<k, TT>::paint;
+        with_bool(sorted, [&](auto sd) {
+            with_bool(whole, [&](auto wh) {
+                with_elsize(pos.elsize, [&](auto pe) {
+                    paint_tile_kernel<k, TT, TH, sd, md, wh, pe><<<pgrid, TH, 0, st>>>(pp, g, (char *)cv, pos, mass, ms, pl->list, pl->offsets,
+                                                                                    pl->counts, hl, ow, mstats, odd, dexp, p);
+                });
+            });
+        });
+    };
+    auto tiles32 = [&](auto k, auto sg) {
+        constexpr int TH = Tile32<k>::threads;
+        with_bool(sorted, [&](auto sd) {
+            with_bool(whole, [&](auto wh) {
+                auto launch = [&](auto pe) {
+                    paint_tile32_kernel<k, TH, sd, sg, wh, pe><<<pgrid, TH, 0, st>>>(p, g, (char *)canvas, pos, mass, ms, pl->list, pl->offsets,
+                                                                                  pl->counts, (float *)halo, overwrite, mstats, 0);
+                };
+                if (dense32) with_elsize(pos.elsize, launch);
+                else if constexpr (!sd) launch(int_c<0>{});
+            });
+        });
+    };
     // the pieces of crowded tiles (none for a uniform batch: the kernel then returns at once)
     const unsigned hgrid = ents ? 0u : (unsigned)(pl->cap_heavy < 1024 ? pl->cap_heavy : 1024);
-#define PH3(K, TT, MD, ODD, PP, CV) do { if (sorted) paint_heavy_kernel<K, TT, TileThreads<K, TT>::paint, true, MD><<<hgrid, TileThreads<K, TT>::paint, 0, st>>>(PP, g, (char *)(CV), pos, mass, ms, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, mstats, ODD, dexp, p); \
-                   else paint_heavy_kernel<K, TT, TileThreads<K, TT>::paint, false, MD><<<hgrid, TileThreads<K, TT>::paint, 0, st>>>(PP, g, (char *)(CV), pos, mass, ms, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, mstats, ODD, dexp, p); } while (0)
-#define PH(K) do { if (run_fixed && det) PH3(K, double, 2, 0, pd, pl->dscratch); \
-                   else if (run_fixed) PH3(K, T, 1, 0, p, canvas); \
-                   if (run_float) PH3(K, T, 0, (run_fixed ? 1 : 0), p, canvas); } while (0)
-    if (hgrid > 0) switch (p.kind) {
-    case PMX_TUNED_NNB: PH(PMX_TUNED_NNB); break;
-    case PMX_TUNED_CIC: PH(PMX_TUNED_CIC); break;
-    case PMX_TUNED_TSC: PH(PMX_TUNED_TSC); break;
-    default: PH(PMX_TUNED_PCS); break;
-    }
-#undef PH
-#undef PH3
+    auto heavy = [&](auto k, auto tt, auto md, int odd, const pmx_painter &pp, void *cv) {
+        using TT = typename decltype(tt)::type;
+        constexpr int TH = TileThreads<k, TT>::paint;
+        with_bool(sorted, [&](auto sd) {
+            paint_heavy_kernel<k, TT, TH, sd, md><<<hgrid, TH, 0, st>>>(pp, g, (char *)cv, pos, mass, ms, pl->list, pl->offsets, pl->counts,
+                                                                      pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, mstats, odd, dexp, p);
+        });
+    };
+    with_kind(p.kind, [&](auto k) {
+        constexpr int S = Tuned<k>::S;
+        const bool entry_form = k == PMX_TUNED_CIC && ents;
+        if constexpr (k == PMX_TUNED_CIC) {
+            constexpr int TH = TileThreads<k, T>::paint;
+            if (entry_form)
+                paint_entries_kernel<k, T, TH, 0, true, 8><<<pgrid, TH, 0, st>>>(p, g, (char *)canvas, pos, mass, ms, (const uint2 *)pl->ents, pl->offsets,
+                                                                                pl->counts, halo, overwrite, mstats, 0, dexp, p);
+        }
+        if (!entry_form) {
+            if (run_fixed && det) tiles(k, type_c<double>{}, int_c<2>{}, 0, pd, pl->dscratch, dhalo, 1);
+            else if (run_fixed) {
+                if constexpr (std::is_same<T, float>::value && S >= 3) with_bool(signed32, [&](auto sg) { tiles32(k, sg); });
+                else tiles(k, type_c<T>{}, int_c<1>{}, 0, p, canvas, halo, overwrite);
+            }
+            if (run_float) tiles(k, type_c<T>{}, int_c<0>{}, run_fixed ? 1 : 0, p, canvas, halo, overwrite);
+        }
+        // (a batch is served either by the fixed-point or by the floating-point kernels: the merge of the other
+        // finds only zeros in its staging buffer... the deterministic one has a staging buffer of its own)
+        if constexpr (S >= 2) {
+            if (!defer) {
+                if (run_fixed && det) {
+                    halo_merge_kernel<S, double, true><<<grid, TBLOCK, 0, st>>>(pd, g, (char *)pl->dscratch, dhalo, pl->counts, 1, mstats, 0);
+                    if (run_float) halo_merge_kernel<S, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, halo, pl->counts, overwrite, mstats, 1);
+                } else halo_merge_kernel<S, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, halo, pl->counts, overwrite);
+            }
+        }
+        if (hgrid > 0) {
+            if (run_fixed && det) heavy(k, type_c<double>{}, int_c<2>{}, 0, pd, pl->dscratch);
+            else if (run_fixed) heavy(k, type_c<T>{}, int_c<1>{}, 0, p, canvas);
+            if (run_float) heavy(k, type_c<T>{}, int_c<0>{}, run_fixed ? 1 : 0, p, canvas);
+        }
+    });
     if (run_fixed && det) {
         const int64_t cells = p.size[0] * p.size[1] * p.size[2];
         det_finish_kernel<T><<<grid_for(cells, TBLOCK, 8192), TBLOCK, 0, st>>>(p, (char *)canvas, (const long long *)pl->dscratch, dexp, overwrite, mstats);
@@ -3681,16 +3563,19 @@ extern "C" int pmx_halo_merge(pmx_binplan *pl, const pmx_painter *p_, void *canv
     const pmx_painter p = *p_;
     const BinGeom &g = pl->g;
     hipStream_t st = (hipStream_t)stream;
-    unsigned grid = (unsigned)(g.ntiles < 65535 * 8 ? g.ntiles : 65535 * 8);
-#define HMD(S_) do { if (p.canvas_elsize == 8) halo_merge_kernel<S_, double><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, (const double *)pl->halo, pl->counts, 1); \
-                     else halo_merge_kernel<S_, float><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, (const float *)pl->halo, pl->counts, 1); } while (0)
+    const unsigned grid = grid_cap(g.ntiles);
+    auto merge = [&](auto s) {
+        with_canvas(p.canvas_elsize, [&](auto c) {
+            using T = typename decltype(c)::type;
+            halo_merge_kernel<s, T><<<grid, TBLOCK, 0, st>>>(p, g, (char *)canvas, (const T *)pl->halo, pl->counts, 1);
+        });
+    };
     switch (g.S) {
-    case 2: HMD(2); break;
-    case 3: HMD(3); break;
-    case 4: HMD(4); break;
+    case 2: merge(int_c<2>{}); break;
+    case 3: merge(int_c<3>{}); break;
+    case 4: merge(int_c<4>{}); break;
     default: break;
     }
-#undef HMD
     pl->halo_pending = 0;
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
@@ -3751,91 +3636,48 @@ extern "C" int pmx_readout_binned(pmx_binplan *pl, const pmx_painter *p_, const 
         dout.data = (const char *)pl->out_sorted;
         dout.stride0 = 8; dout.stride1 = 0; dout.elsize = 8;
     }
-    unsigned grid = (unsigned)(g.ntiles < 65535 * 8 ? g.ntiles : 65535 * 8);
+    const unsigned grid = grid_cap(g.ntiles);
     const bool relax = pl->exact == 0;
     // [r5] the common case — relaxed arithmetic, the index list, dense position rows, a dense result vector — has a loop of its
     // own, which also zeroes the dropped particles and takes the pieces of crowded tiles (one launch instead of three)
-#ifndef PMX_LEAN_READOUT
-#define PMX_LEAN_READOUT 1
-#endif
-    const bool lean = PMX_LEAN_READOUT && relax && !sorted && dpos.stride1 == dpos.elsize && dpos.stride0 == 3 * dpos.elsize
+    const bool lean = relax && !sorted && dpos.stride1 == dpos.elsize && dpos.stride0 == 3 * dpos.elsize
                       && dout.stride0 >= dout.elsize && dout.stride0 % dout.elsize == 0 && dout.stride0 < (1 << 20);      // (a dense vector, or a column of the caller's array: F[:, d])
     if (!lean) zero_dropped_kernel<<<256, TBLOCK, 0, st>>>(pl->list, pl->offsets, pl->counts, g.ntiles, dout, sorted);
     // (NNB: one cell, weight 1 — the same bits either way; the lean per-particle setup of the relaxed form is what it takes)
-#define RT2(K, T, RX) do { if (sorted) readout_tile_kernel<K, T, TileThreads<K, T>::readout, true, RX><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts); \
-                      else readout_tile_kernel<K, T, TileThreads<K, T>::readout, false, RX><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts); } while (0)
-#define RT(K, T) do { if (relax) RT2(K, T, true); else RT2(K, T, false); } while (0)
-    bool whole_r = true;
-    for (int d = 0; d < 3; d++) whole_r = whole_r && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];      // (whole_mesh())
-#ifdef PMX_GENERAL_FORMS_ONLY
-    whole_r = false;       // (a build switch for measurements, right results: what the forms for blocks of any shape cost on a whole mesh)
-#endif
-#define RLL(K, T, PE_, OE_, WH) do { if (K == PMX_TUNED_CIC && PE_ == 8 && WH && pl->blocks) \
-        readout_entries_kernel<PMX_TUNED_CIC, T, TileThreads<PMX_TUNED_CIC, T>::readout, 8, OE_, true><<<grid, TileThreads<PMX_TUNED_CIC, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data), (const uint2 *)pl->ents, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, 0u, (int)dout.stride0); \
-    else readout_tile_lean_kernel<K, T, TileThreads<K, T>::readout, PE_, OE_, WH><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data), pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, (int)dout.stride0); } while (0)
-#define RLW(K, T, PE_, OE_) do { if (whole_r) RLL(K, T, PE_, OE_, true); else RLL(K, T, PE_, OE_, false); } while (0)
-#define RLO(K, T, PE_) do { if (dout.elsize == 8) RLW(K, T, PE_, 8); else RLW(K, T, PE_, 4); } while (0)
-#define RL(K, T) do { if (dpos.elsize == 8) RLO(K, T, 8); else RLO(K, T, 4); } while (0)
-    if (lean) {
-        if (p.canvas_elsize == 8) {
-            switch (p.kind) {
-            case PMX_TUNED_NNB: RL(PMX_TUNED_NNB, double); break;
-            case PMX_TUNED_CIC: RL(PMX_TUNED_CIC, double); break;
-            case PMX_TUNED_TSC: RL(PMX_TUNED_TSC, double); break;
-            default: RL(PMX_TUNED_PCS, double); break;
+    const unsigned hgrid = (unsigned)(pl->cap_heavy < 1024 ? pl->cap_heavy : 1024);
+    with_canvas(p.canvas_elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_kind(p.kind, [&](auto k) {
+            constexpr int TH = TileThreads<k, T>::readout;
+            if (lean) {
+                with_elsize(dpos.elsize, [&](auto pe) {
+                    with_elsize(dout.elsize, [&](auto oe) {
+                        with_bool(whole_mesh(p, g), [&](auto wh) {
+                            if constexpr (k == PMX_TUNED_CIC && pe == 8 && wh) {
+                                if (pl->blocks) {
+                                    readout_entries_kernel<k, T, TH, 8, oe, true><<<grid, TH, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data),
+                                                                                                      (const uint2 *)pl->ents, pl->offsets, pl->counts, pl->heavy_items,
+                                                                                                      pl->nheavy, 0u, (int)dout.stride0);
+                                    return;
+                                }
+                            }
+                            readout_tile_lean_kernel<k, T, TH, pe, oe, wh><<<grid, TH, 0, st>>>(p, g, (const char *)canvas, dpos, (char *)const_cast<char *>(dout.data),
+                                                                                            pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy,
+                                                                                            (uint32_t)pl->cap_heavy, (int)dout.stride0);
+                        });
+                    });
+                });
+                return;
             }
-        } else {
-            switch (p.kind) {
-            case PMX_TUNED_NNB: RL(PMX_TUNED_NNB, float); break;
-            case PMX_TUNED_CIC: RL(PMX_TUNED_CIC, float); break;
-            case PMX_TUNED_TSC: RL(PMX_TUNED_TSC, float); break;
-            default: RL(PMX_TUNED_PCS, float); break;
-            }
-        }
-    } else
-#undef RL
-#undef RLO
-#undef RLW
-    if (p.canvas_elsize == 8) {
-        switch (p.kind) {
-        case PMX_TUNED_NNB: RT(PMX_TUNED_NNB, double); break;
-        case PMX_TUNED_CIC: RT(PMX_TUNED_CIC, double); break;
-        case PMX_TUNED_TSC: RT(PMX_TUNED_TSC, double); break;
-        default: RT(PMX_TUNED_PCS, double); break;
-        }
-    } else {
-        switch (p.kind) {
-        case PMX_TUNED_NNB: RT(PMX_TUNED_NNB, float); break;
-        case PMX_TUNED_CIC: RT(PMX_TUNED_CIC, float); break;
-        case PMX_TUNED_TSC: RT(PMX_TUNED_TSC, float); break;
-        default: RT(PMX_TUNED_PCS, float); break;
-        }
-    }
-#undef RT
-#undef RT2
-    if (!lean) {
-        const unsigned hgrid = (unsigned)(pl->cap_heavy < 1024 ? pl->cap_heavy : 1024);
-#define RH2(K, T, RX) do { if (sorted) readout_heavy_kernel<K, T, TileThreads<K, T>::readout, true, RX><<<hgrid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy); \
-                      else readout_heavy_kernel<K, T, TileThreads<K, T>::readout, false, RX><<<hgrid, TileThreads<K, T>::readout, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy); } while (0)
-#define RH(K, T) do { if (relax) RH2(K, T, true); else RH2(K, T, false); } while (0)
-        if (p.canvas_elsize == 8) {
-            switch (p.kind) {
-            case PMX_TUNED_NNB: RH(PMX_TUNED_NNB, double); break;
-            case PMX_TUNED_CIC: RH(PMX_TUNED_CIC, double); break;
-            case PMX_TUNED_TSC: RH(PMX_TUNED_TSC, double); break;
-            default: RH(PMX_TUNED_PCS, double); break;
-            }
-        } else {
-            switch (p.kind) {
-            case PMX_TUNED_NNB: RH(PMX_TUNED_NNB, float); break;
-            case PMX_TUNED_CIC: RH(PMX_TUNED_CIC, float); break;
-            case PMX_TUNED_TSC: RH(PMX_TUNED_TSC, float); break;
-            default: RH(PMX_TUNED_PCS, float); break;
-            }
-        }
-#undef RH
-#undef RH2
-    }
+            with_bool(sorted, [&](auto sd) {
+                with_bool(relax, [&](auto rx) {
+                    readout_tile_kernel<k, T, TH, sd, rx><<<grid, TH, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts);
+                    readout_heavy_kernel<k, T, TH, sd, rx><<<hgrid, TH, 0, st>>>(p, g, (const char *)canvas, dpos, dout, pl->list, pl->offsets, pl->counts,
+                                                                              pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy);
+                });
+            });
+        });
+    });
     if (sorted)
         unsort_kernel<<<grid_for(pl->npart, TBLOCK), TBLOCK, 0, st>>>(pl->out_sorted, pl->inv, pl->npart, caller_out);
     PMX_HIP_CHECK(hipGetLastError());
@@ -3866,32 +3708,22 @@ extern "C" int pmx_readout_binned_multi(pmx_binplan *pl, const pmx_painter *p_, 
     for (int f = 0; f < PMX_MAXFIELDS; f++) cs.ptr[f] = f < ncanvas ? (const char *)canvases[f] : nullptr;
     cs.n = ncanvas;
     cs.ostride1 = (int32_t)dout.stride1;
-    const unsigned grid = (unsigned)(g.ntiles < 65535 * 8 ? g.ntiles : 65535 * 8);
-    bool whole_r = true;
-    for (int d = 0; d < 3; d++) whole_r = whole_r && g.o[d] == 0 && (int)p.period[d] == (int)p.size[d];
-#define RML(K, T, PE_, OE_, WH) readout_tile_multi_kernel<K, T, TileThreads<K, T>::readout, PE_, OE_, WH><<<grid, TileThreads<K, T>::readout, 0, st>>>(p, g, cs, dpos, (char *)const_cast<char *>(dout.data), pl->list, pl->offsets, pl->counts, pl->heavy_items, pl->nheavy, (uint32_t)pl->cap_heavy, (int)dout.stride0)
-#define RMW(K, T, PE_, OE_) do { if (whole_r) RML(K, T, PE_, OE_, true); else RML(K, T, PE_, OE_, false); } while (0)
-#define RMO(K, T, PE_) do { if (dout.elsize == 8) RMW(K, T, PE_, 8); else RMW(K, T, PE_, 4); } while (0)
-#define RM(K, T) do { if (dpos.elsize == 8) RMO(K, T, 8); else RMO(K, T, 4); } while (0)
-    if (p.canvas_elsize == 8) {
-        switch (p.kind) {
-        case PMX_TUNED_NNB: RM(PMX_TUNED_NNB, double); break;
-        case PMX_TUNED_CIC: RM(PMX_TUNED_CIC, double); break;
-        case PMX_TUNED_TSC: RM(PMX_TUNED_TSC, double); break;
-        default: RM(PMX_TUNED_PCS, double); break;
-        }
-    } else {
-        switch (p.kind) {
-        case PMX_TUNED_NNB: RM(PMX_TUNED_NNB, float); break;
-        case PMX_TUNED_CIC: RM(PMX_TUNED_CIC, float); break;
-        case PMX_TUNED_TSC: RM(PMX_TUNED_TSC, float); break;
-        default: RM(PMX_TUNED_PCS, float); break;
-        }
-    }
-#undef RM
-#undef RMO
-#undef RMW
-#undef RML
+    const unsigned grid = grid_cap(g.ntiles);
+    with_canvas(p.canvas_elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_kind(p.kind, [&](auto k) {
+            constexpr int TH = TileThreads<k, T>::readout;
+            with_elsize(dpos.elsize, [&](auto pe) {
+                with_elsize(dout.elsize, [&](auto oe) {
+                    with_bool(whole_mesh(p, g), [&](auto wh) {
+                        readout_tile_multi_kernel<k, T, TH, pe, oe, wh><<<grid, TH, 0, st>>>(p, g, cs, dpos, (char *)const_cast<char *>(dout.data), pl->list,
+                                                                                         pl->offsets, pl->counts, pl->heavy_items, pl->nheavy,
+                                                                                         (uint32_t)pl->cap_heavy, (int)dout.stride0);
+                    });
+                });
+            });
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """The FIRST build of a bin plan (two passes: count, fill) on rows in tile order under strong clustering: a fraction f of
-512^3 particles in `nb` Gaussian blobs of sigma cells.  PMESH_AMD_LIBRARY selects the build (scripts/build_variant.sh
-twopass0 "-DPMX_LEAN_TWOPASS=0": the per-wave count and scatter kernels)."""
+512^3 particles in `nb` Gaussian blobs of sigma cells."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
