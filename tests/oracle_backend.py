@@ -125,6 +125,12 @@ class OracleBackend(object):
         y = numpy.fft.ifft(x, axis=1) * N if inverse else numpy.fft.fft(x, axis=1)
         arr[...] = y * scale
 
+    def colfft_to(self, elsize, inverse, src, dst, A, N, B, scale=1.0, transfer=None, n1=1, n2=1,
+                  start=(0, 0, 0), nmesh=(1, 1, 1), boxsize=(1.0, 1.0, 1.0), a_stride=0, n_stride=0):
+        dst.copy_(src)
+        self.colfft(elsize, inverse, dst, A, N, B, scale=scale, transfer=transfer, n1=n1, n2=n2, start=start,
+                    nmesh=nmesh, boxsize=boxsize, a_stride=a_stride, n_stride=n_stride)
+
     def colfft_configure(self, persistent):
         pass
 

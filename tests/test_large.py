@@ -4,7 +4,8 @@
 indices everywhere: the tile-binned and the direct paint/readout must agree, mass must be conserved
 with the last planes holding their share, and r2c -> c2r must return the field (rocFFT's own 3-d
 transform returns wrong numbers at this size, which is why pmx_fft_create refuses it and the own
-row/column kernels cover 2048).  Size-independent properties only: no oracle run at this size.
+row/column kernels cover 2048).  No oracle run at this size: size-independent properties, and an analytic answer
+for r2c / c2r (a sum of cosines).
 """
 import ctypes as C
 
@@ -59,6 +60,89 @@ def test_mesh_beyond_32bit_cells():
     back = a.r2c(out=Ellipsis).c2r(out=Ellipsis)
     assert float((back.value[N - 8:] - hi).abs().max()) < 1e-5
     assert float((back.value[:8] - lo).abs().max()) < 1e-5
+    backend.reset()
+
+
+def test_r2c_c2r_known_answer_beyond_32bit_elements():
+    """2048^3 in fp32 on one rank against an analytic answer: a sum of cosines A cos(2 pi k.x / N + phi) at chosen
+    wavevectors — odd indices, the Nyquist index of each axis, one in the k2 = 0 plane (whose conjugate is stored too)
+    and two whose stored modes lie past complex element 2^31 and 2^32 of the spectrum in the layout r2c returns.  r2c
+    must put A e^(+-i phi) / 2 at exactly those modes and their stored conjugates (to 1e-6) and leave every other
+    mode below 1e-6; c2r of the exact sparse spectrum must give the cosines on sampled planes, the last 8 among
+    them.  Built and reduced on the device one chunk of planes at a time (no mesh-sized temporaries, no host copy)."""
+    import gc
+    import math
+    from pmesh_amd import backend
+    from pmesh_amd.pm import ParticleMesh
+    backend.reset()
+    be = backend.get()
+    gc.collect()                                   # (the 34 GB fields of the test above wait in the allocator's cache)
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info()
+    if free < 120e9:
+        pytest.skip('needs ~100 GB of free HBM')
+    torch.cuda.reset_peak_memory_stats()
+    N, h, P = 2048, 1024, 32
+    dev = be.device
+    modes = [((3, 5, 7), 1.0, 0.3), ((h, 3, 9), 0.75, 1.1), ((11, h, 5), 0.5, -0.7), ((7, 13, h), 1.25, 0.9),
+             ((21, 17, 0), 0.625, 2.0), ((1537, 1001, 999), 1.5, -1.3), ((N - 1, N - 1, h - 1), 0.875, 0.5)]
+    x1 = torch.arange(N, device=dev, dtype=torch.int64).view(1, N, 1)
+    x2 = torch.arange(N, device=dev, dtype=torch.int64).view(1, 1, N)
+
+    def cosines(a, n):
+        """the field on planes [a, a + n) in float64"""
+        x0 = torch.arange(a, a + n, device=dev, dtype=torch.int64).view(n, 1, 1)
+        acc = torch.zeros((n, N, N), dtype=torch.float64, device=dev)
+        for (k0, k1, k2), A, phi in modes:
+            m = (k0 * x0 + k1 * x1 + k2 * x2) % N            # (exact phase index: no rounding of k.x)
+            acc += A * torch.cos(m.double() * (2 * math.pi / N) + phi)
+        return acc
+
+    pm = ParticleMesh(BoxSize=1000.0, Nmesh=[N, N, N], dtype='f4')
+    real = pm.create('real')
+    for a in range(0, N, P):
+        real.value[a:a + P] = cosines(a, P).float()
+    ck = real.r2c(out=Ellipsis)
+    cv = ck.value
+    assert tuple(cv.shape) == (N, N, h + 1)
+    # the stored modes: A e^(i phi) / 2 at k, its conjugate at -k where that has k2 <= N / 2
+    want = {}
+    for k, A, phi in modes:
+        for sgn in (1, -1):
+            q = tuple((sgn * kk) % N for kk in k)
+            if q[2] <= h:
+                want[q] = want.get(q, 0) + A / 2 * complex(math.cos(phi), sgn * math.sin(phi))
+    assert (h, 3, 9) in want and (N - 7, N - 13, h) in want and (N - 21, N - 17, 0) in want and len(want) == 9
+    off = lambda q: cv.storage_offset() + sum(i * s for i, s in zip(q, cv.stride()))
+    assert off((1537, 1001, 999)) > 2 ** 31 and off((N - 1, N - 1, h - 1)) > 2 ** 32, cv.stride()
+    worst_mode, worst_else = 0.0, 0.0
+    for a in range(0, N, P):
+        got = cv[a:a + P].to(torch.complex128)
+        exp = torch.zeros_like(got)
+        for q, v in want.items():
+            if a <= q[0] < a + P:
+                exp[q[0] - a, q[1], q[2]] = v
+        d = (got - exp).abs()
+        on = exp != 0
+        if bool(on.any()):
+            worst_mode = max(worst_mode, float(d[on].max()))
+            d[on] = 0
+        worst_else = max(worst_else, float(d.max()))
+    print('r2c: worst error at the modes %.2e, largest other mode %.2e' % (worst_mode, worst_else))
+    assert worst_mode < 1e-6 and worst_else < 1e-6, (worst_mode, worst_else)       # (measured 5.3e-8, 3.4e-8)
+    # c2r of the exact sparse spectrum
+    for a in range(0, N, P):
+        cv[a:a + P] = 0
+    for q, v in want.items():
+        cv[q] = v
+    back = ck.c2r(out=Ellipsis)
+    worst = 0.0
+    for i in [0, 1, 777, 1024, 1537] + list(range(N - 8, N)):
+        worst = max(worst, float((back.value[i].double() - cosines(i, 1)[0]).abs().max()))
+    print('c2r: worst error on the sampled planes %.2e; peak device memory %.1f GB'
+          % (worst, torch.cuda.max_memory_allocated() / 1e9))
+    assert worst < 2e-5, worst                     # (measured 1.7e-6 for cosines of amplitudes summing to 6.5)
+    del real, ck, back, cv
     backend.reset()
 
 
