@@ -521,6 +521,53 @@ int pmx_power_project(const pmx_power *p, int32_t ndim, int32_t elsize, const vo
                       const int64_t *nmesh, const double *boxsize, const double *kedges, const double *muedges,
                       double *acc, void *stream);
 
+/* ---- initial conditions: tabulated transfers and second-order LPT (the reference's examples/nbody.py:245-282 builds
+ * its linear field with a tabulated P(k) through Field.apply; nbody/genic.py:121-166 the 2LPT displacements) --------
+ * Geometry as in pmx_apply_transfer: a local block of logical shape[0..ndim) at global index start[], byte strides
+ * per array, ndim 1..3, elsize 4 or 8 per (real) component.  Wavenumbers as there: k_d = w_d N_d / L_d with
+ * w_d = 2 pi / N_d * (i - N_d [i >= N_d / 2]), k^2 = (k_0^2 + k_1^2) + k_2^2, all in double. */
+
+#define PMX_KTABLE_MAX 8192            /* entries of a pmx_ktable */
+
+typedef struct pmx_ktable {
+    int32_t n;                         /* entries: 2 .. PMX_KTABLE_MAX */
+    int32_t loglog;                    /* 0: x = k, y = t;  1: x = ln k, y = ln t (the caller takes the logarithms) */
+    double amplitude;
+    double left, right;                /* T below the first / above the last tabulated k */
+    double kmin, kmax;                 /* the first and last tabulated k (not their logarithms) */
+    double inv_step;                   /* > 0: x is uniform with step 1 / inv_step (the search starts from a closed-form
+                                          guess; any x still gives the same result); 0: no guess */
+    const double *x;                   /* device: n strictly increasing values */
+    const double *y;                   /* device: n values */
+} pmx_ktable;
+
+/* out[m] = T(|k|) * in[m] over a complex block, |k| = sqrt(k^2); in may equal out.
+ *   T(|k|) = amplitude * left       for |k| < kmin
+ *            amplitude * right      for |k| > kmax
+ *            amplitude * f(u)       otherwise, u = |k| (loglog = 0) or ln |k| (loglog = 1),
+ * where g(u) = y[j] + s_j (u - x[j]) for x[j] <= u < x[j + 1], s_j = (y[j + 1] - y[j]) / (x[j + 1] - x[j]), clamped to
+ * y[0] / y[n - 1] outside [x[0], x[n - 1]] (numpy.interp), and f = g (loglog = 0) or exp(g) (loglog = 1).  j is found by
+ * binary search over x in device memory, from the guess (u - x[0]) inv_step when inv_step > 0.  n outside 2 .. PMX_KTABLE_MAX returns PMX_EUNSUPPORTED. */
+int pmx_apply_ktable(const pmx_ktable *t, int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides,
+                     void *out, const int64_t *out_strides, const int64_t *shape, const int64_t *start,
+                     const int64_t *nmesh, const double *boxsize, void *stream);
+
+/* Reads the complex block `in` once and writes, for each of nout (1..3) pairs (i, j) = (pairs[2 p], pairs[2 p + 1]),
+ * out[p][m] = (k_i k_j / k^2) * in[m] (0 at k = 0) with byte strides out_strides[3 p .. 3 p + 3).  pairs, out and
+ * out_strides are host arrays; an out[p] may be `in` itself when it has in's strides. */
+int pmx_lpt_hessian(int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides, int32_t nout,
+                    const int32_t *pairs, void *const *out, const int64_t *out_strides, const int64_t *shape,
+                    const int64_t *start, const int64_t *nmesh, const double *boxsize, void *stream);
+
+/* The second-order LPT source over real blocks: in (host array of device pointers) holds ndim diagonal components
+ * phi_00 .. phi_{ndim-1 ndim-1}, then the off-diagonal ones phi_01 (2-d); phi_01, phi_02, phi_12 (3-d), byte strides
+ * in_strides[3 q .. 3 q + 3) each.  Writes, in double and in this order of operations,
+ *   out = scale * (phi_00 phi_11 - phi_01 phi_01)                                                          (2-d)
+ *   out = scale * (((((phi_00 phi_11 + phi_11 phi_22) + phi_22 phi_00) - phi_01^2) - phi_02^2) - phi_12^2)  (3-d)
+ * out may equal in[0] (same strides); ndim 2 or 3. */
+int pmx_lpt2_source(int32_t ndim, int32_t elsize, const void *const *in, const int64_t *in_strides, void *out,
+                    const int64_t *out_strides, const int64_t *shape, double scale, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

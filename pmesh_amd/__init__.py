@@ -3,8 +3,9 @@
     from pmesh_amd.pm import ParticleMesh, RealField, ComplexField
     from pmesh_amd.window import ResampleWindow, Affine, CIC, TSC, PCS
     from pmesh_amd.domain import GridND, Layout
-    from pmesh_amd.transfer import Transfer
+    from pmesh_amd.transfer import Transfer, Tabulated
     from pmesh_amd.power import power_spectrum     # binned P(k), P(k, mu), multipoles
+    from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
 
 Host code is Python; all arithmetic is in libpmesh_amd.so (hand-written HIP
 kernels + rocFFT behind the C ABI of include/pmesh_amd.h).  Importing the

@@ -94,6 +94,18 @@ class Power(C.Structure):
     ]
 
 
+PMX_KTABLE_MAX = 8192
+
+
+class KTable(C.Structure):
+    """pmx_ktable (include/pmesh_amd.h): the table of pmx_apply_ktable (x, y: device arrays of float64)"""
+    _fields_ = [
+        ('n', C.c_int32), ('loglog', C.c_int32), ('amplitude', C.c_double), ('left', C.c_double),
+        ('right', C.c_double), ('kmin', C.c_double), ('kmax', C.c_double), ('inv_step', C.c_double),
+        ('x', C.c_void_p), ('y', C.c_void_p),
+    ]
+
+
 _P = C.POINTER
 _vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 
@@ -174,6 +186,11 @@ DEVICE_ONLY = {
     'slab_unpack': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _P(_i64), _i32, _i32, _vp]),
     'power_project': (C.c_int, [_P(Power), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
                                 _P(_f64), _vp, _vp, _vp, _vp]),
+    'apply_ktable': (C.c_int, [_P(KTable), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
+                               _P(_f64), _vp]),
+    'lpt_hessian': (C.c_int, [_i32, _i32, _vp, _P(_i64), _i32, _P(C.c_int32), _P(_vp), _P(_i64), _P(_i64), _P(_i64),
+                              _P(_i64), _P(_f64), _vp]),
+    'lpt2_source': (C.c_int, [_i32, _i32, _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _f64, _vp]),
 }
 
 

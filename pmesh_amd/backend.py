@@ -218,6 +218,37 @@ class HipBackend(object):
                   kedges.data_ptr(), muedges.data_ptr() if muedges is not None else None, acc.data_ptr(),
                   self.stream())
 
+    # -- initial conditions: tabulated transfer, 2LPT ----------------------
+    def apply_ktable(self, table, v, out, start, nmesh, boxsize):
+        """out = T(|k|) v over the local complex block v (pmx_apply_ktable; `table` a _abi.KTable whose x / y are
+        float64 device arrays kept alive by the caller); out may be v"""
+        es = v.element_size()
+        self.call('apply_ktable', C.byref(table), v.dim(), es // 2, v.data_ptr(), _abi.i64arr([s * es for s in v.stride()], 3),
+                  out.data_ptr(), _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(v.shape, 3),
+                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+
+    def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
+        """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
+        (pmx_lpt_hessian)"""
+        es = v.element_size()
+        n = len(outs)
+        ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        strides = _abi.i64arr([s * es for o in outs for s in (list(o.stride()) + [0] * 3)[:3]])
+        flat = (C.c_int32 * (2 * n))(*[int(x) for p in pairs for x in p])
+        self.call('lpt_hessian', v.dim(), es // 2, v.data_ptr(), _abi.i64arr([s * es for s in v.stride()], 3), n, flat,
+                  ptrs, strides, _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3),
+                  _abi.f64arr(boxsize, 3), self.stream())
+
+    def lpt2_source(self, ins, out, scale):
+        """out = scale * S(phi_ij) over real blocks: ins = the diagonal, then the off-diagonal components
+        (pmx_lpt2_source); out may be ins[0]"""
+        es = out.element_size()
+        ptrs = (C.c_void_p * len(ins))(*[a.data_ptr() for a in ins])
+        strides = _abi.i64arr([s * es for a in ins for s in (list(a.stride()) + [0] * 3)[:3]])
+        self.call('lpt2_source', out.dim(), es, ptrs, strides, out.data_ptr(),
+                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3), float(scale),
+                  self.stream())
+
 
 _current = None
 

@@ -52,6 +52,8 @@ cdef extern from "pmesh_amd.h" nogil:
         pass
     ctypedef struct pmx_power:
         pass
+    ctypedef struct pmx_ktable:
+        pass
 
 _bound = None
 

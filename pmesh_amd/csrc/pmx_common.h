@@ -77,6 +77,16 @@ template <int PE> __device__ __forceinline__ double pos_get(const DVec &pos, int
     return PE == 8 ? *(const double *)q : (double)*(const float *)q;
 }
 
+// The wavenumber of global index gi along an axis of n cells: w = 2 pi / n (gi - n [gi >= n / 2]), k = w n / L, with
+// dw = 2 pi / n and nl = n / L — the sequence of roundings of transfer_kernel (pmx_transfer.hip) and ComplexField.x.
+__device__ __forceinline__ double wavenumber(int64_t gi, int64_t n, double dw, double nl)
+{
+    double wi = (double)gi;
+    if (gi >= n / 2) wi -= n;
+    wi *= dw;
+    return wi * nl;
+}
+
 inline DVec dvec(const pmx_vec *v)
 {
     DVec d;

@@ -1,0 +1,345 @@
+// pmx_lpt.hip — initial conditions: a tabulated transfer T(|k|), the Hessian spectra k_i k_j / k^2 of the linear
+// density and the second-order LPT source built from them (include/pmesh_amd.h: pmx_apply_ktable, pmx_lpt_hessian,
+// pmx_lpt2_source).
+//
+// Replaces the host slab loop Field.apply falls back to for a numpy.interp transfer (the reference's
+// examples/nbody.py:245-282) and the chain of per-component apply calls and products of the reference's
+// nbody/genic.py:121-166.  All three kernels stream: one read and one write per element (the Hessian kernel one read
+// and up to three writes, the source kernel one read of each of its 3 or 6 inputs), one thread per element in memory
+// order, wavenumbers recomputed from the index with the roundings of transfer_kernel (pmx_common.h: wavenumber).
+// The table of pmx_apply_ktable stays in device memory: a wave's neighbouring modes walk the same few lines of it,
+// which the L1 / L2 serve, and no workgroup pays for loading a whole table into LDS.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "pmx_common.h"
+
+namespace pmx {
+
+struct LGeom {
+    int64_t shape[3], start[3], nmesh[3];   // logical order
+    double dw[3], nl[3];                    // 2 pi / N and N / L per axis
+    int32_t ax[3];                          // memory-order permutation: ax[2] varies fastest
+    int32_t ndim;
+};
+
+struct LStr {
+    int64_t s[3];                           // byte strides, logical order
+    __device__ __forceinline__ int64_t off(const int64_t *idx) const { return idx[0] * s[0] + idx[1] * s[1] + idx[2] * s[2]; }
+};
+
+struct HOut {
+    char *p[3];
+    LStr s[3];
+    int32_t i[3], j[3];
+};
+
+struct SIn {
+    const char *p[6];
+    LStr s[6];
+};
+
+// grid.y walks the slowest memory axis, grid.x / threads the flattened two fast axes (as transfer_kernel): 32-bit
+// index arithmetic inside a plane, consecutive threads on consecutive elements
+#define PMX_LPT_LOOP(g)                                                                                            \
+    const uint32_t n1_ = (uint32_t)(g).shape[(g).ax[1]], n2_ = (uint32_t)(g).shape[(g).ax[2]];                     \
+    const uint32_t inner_ = n1_ * n2_;                                                                             \
+    for (int64_t i0_ = blockIdx.y; i0_ < (g).shape[(g).ax[0]]; i0_ += gridDim.y)                                   \
+    for (uint32_t q_ = blockIdx.x * blockDim.x + threadIdx.x; q_ < inner_; q_ += gridDim.x * blockDim.x)
+
+__device__ __forceinline__ void block_index(const LGeom &g, int64_t i0, uint32_t q, int64_t *idx)
+{
+    const uint32_t n2 = (uint32_t)g.shape[g.ax[2]];
+    const uint32_t i1 = q / n2;
+    const int64_t v0 = i0, v1 = i1, v2 = q - i1 * n2;
+#pragma unroll
+    for (int d = 0; d < 3; d++) idx[d] = (g.ax[0] == d) ? v0 : ((g.ax[1] == d) ? v1 : v2);
+}
+
+// k_d per axis (0 beyond ndim) and k^2 = (k_0^2 + k_1^2) + k_2^2
+__device__ __forceinline__ double wavevector(const LGeom &g, const int64_t *idx, double *kk)
+{
+    double k2 = 0;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        kk[d] = 0;
+        if (d >= g.ndim) continue;
+        kk[d] = wavenumber(idx[d] + g.start[d], g.nmesh[d], g.dw[d], g.nl[d]);
+        k2 += kk[d] * kk[d];
+    }
+    return k2;
+}
+
+template <typename T> struct CLoad;
+template <> struct CLoad<double> {
+    static __device__ __forceinline__ void get(const char *p, double &re, double &im)
+    {
+        double2 v = *(const double2 *)p;
+        re = v.x;
+        im = v.y;
+    }
+    static __device__ __forceinline__ void put(char *p, double re, double im) { *(double2 *)p = make_double2(re, im); }
+};
+template <> struct CLoad<float> {
+    static __device__ __forceinline__ void get(const char *p, double &re, double &im)
+    {
+        float2 v = *(const float2 *)p;
+        re = v.x;
+        im = v.y;
+    }
+    static __device__ __forceinline__ void put(char *p, double re, double im)
+    {
+        *(float2 *)p = make_float2((float)re, (float)im);
+    }
+};
+
+// numpy.interp(u, x, y) with its end values outside [x[0], x[n-1]]: binary search for x[j] <= u < x[j + 1], started
+// from the closed-form guess j = (u - x[0]) * inv_step of a uniform table (inv_step > 0), which narrows the search to
+// one side of the guess and ends it at once when the guess holds
+__device__ __forceinline__ double table_interp(const double *x, const double *y, int n, double inv_step, double u)
+{
+    const double x0 = x[0];
+    if (u <= x0) return y[0];
+    if (u >= x[n - 1]) return y[n - 1];
+    int lo = 0, hi = n - 1;     // x[lo] <= u < x[hi]
+    if (inv_step > 0) {
+        const double t = (u - x0) * inv_step;
+        const int g = t < 0 ? 0 : (t > n - 2 ? n - 2 : (int)t);
+        if (x[g] <= u) {
+            lo = g;
+            if (u < x[g + 1]) hi = g + 1;
+        } else {
+            hi = g;
+        }
+    }
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (x[m] <= u) lo = m;
+        else hi = m;
+    }
+    const double xl = x[lo], yl = y[lo];
+    if (xl == u) return yl;
+    const double s = (y[lo + 1] - yl) / (x[lo + 1] - xl);
+    return s * (u - xl) + yl;
+}
+
+template <typename T, bool LOG>
+__global__ void __launch_bounds__(256) ktable_kernel(pmx_ktable t, LGeom g, const char *in, LStr is, char *out, LStr os)
+{
+    PMX_LPT_LOOP(g) {
+        int64_t idx[3];
+        block_index(g, i0_, q_, idx);
+        double kk[3];
+        const double k = sqrt(wavevector(g, idx, kk));
+        double f;
+        if (k < t.kmin) f = t.left;
+        else if (k > t.kmax) f = t.right;
+        else if (LOG) f = exp(table_interp(t.x, t.y, t.n, t.inv_step, log(k)));
+        else f = table_interp(t.x, t.y, t.n, t.inv_step, k);
+        f = t.amplitude * f;
+        double re, im;
+        CLoad<T>::get(in + is.off(idx), re, im);
+        CLoad<T>::put(out + os.off(idx), f * re, f * im);
+    }
+}
+
+template <typename T, int NOUT>
+__global__ void __launch_bounds__(256) hessian_kernel(LGeom g, const char *in, LStr is, HOut o)
+{
+    PMX_LPT_LOOP(g) {
+        int64_t idx[3];
+        block_index(g, i0_, q_, idx);
+        double kk[3];
+        const double k2 = wavevector(g, idx, kk);
+        double re, im;
+        CLoad<T>::get(in + is.off(idx), re, im);
+#pragma unroll
+        for (int p = 0; p < NOUT; p++) {
+            const double f = (k2 == 0) ? 0.0 : (kk[o.i[p]] * kk[o.j[p]]) / k2;
+            CLoad<T>::put(o.p[p] + o.s[p].off(idx), f * re, f * im);
+        }
+    }
+}
+
+template <typename T> __device__ __forceinline__ double rget(const SIn &a, int q, const int64_t *idx)
+{
+    return (double)*(const T *)(a.p[q] + a.s[q].off(idx));
+}
+
+template <typename T, int ND>
+__global__ void __launch_bounds__(256) lpt2_source_kernel(LGeom g, SIn a, char *out, LStr os, double scale)
+{
+    PMX_LPT_LOOP(g) {
+        int64_t idx[3];
+        block_index(g, i0_, q_, idx);
+        double s;
+        if (ND == 2) {
+            const double p00 = rget<T>(a, 0, idx), p11 = rget<T>(a, 1, idx), p01 = rget<T>(a, 2, idx);
+            s = p00 * p11 - p01 * p01;
+        } else {
+            const double p00 = rget<T>(a, 0, idx), p11 = rget<T>(a, 1, idx), p22 = rget<T>(a, 2, idx);
+            const double p01 = rget<T>(a, 3, idx), p02 = rget<T>(a, 4, idx), p12 = rget<T>(a, 5, idx);
+            s = p00 * p11 + p11 * p22;
+            s = s + p22 * p00;
+            s = s - p01 * p01;
+            s = s - p02 * p02;
+            s = s - p12 * p12;
+        }
+        *(T *)(out + os.off(idx)) = (T)(scale * s);
+    }
+}
+
+#undef PMX_LPT_LOOP
+
+// the block geometry, axes ordered by decreasing |stride| of `order` (the rule of pmx_apply_transfer)
+static LGeom make_geom(int32_t ndim, const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                       const double *boxsize, const int64_t *order)
+{
+    LGeom g;
+    g.ndim = ndim;
+    int64_t os[3];
+    for (int d = 0; d < 3; d++) {
+        const bool on = d < ndim;
+        g.shape[d] = on ? shape[d] : 1;
+        g.start[d] = on && start ? start[d] : 0;
+        g.nmesh[d] = on && nmesh ? nmesh[d] : 1;
+        const double L = on && boxsize ? boxsize[d] : 1.0;
+        g.dw[d] = 2 * M_PI / g.nmesh[d];
+        g.nl[d] = g.nmesh[d] / L;
+        os[d] = on ? order[d] : 0;
+    }
+    int ax[3] = {0, 1, 2};
+    for (int a = 0; a < 3; a++)
+        for (int b = a + 1; b < 3; b++) {
+            int64_t sa = llabs(os[ax[a]]), sb = llabs(os[ax[b]]);
+            bool swap = sa < sb || (sa == sb && g.shape[ax[a]] == 1 && g.shape[ax[b]] != 1);
+            if (swap) { int tmp = ax[a]; ax[a] = ax[b]; ax[b] = tmp; }
+        }
+    for (int a = 0; a < 3; a++) g.ax[a] = ax[a];
+    return g;
+}
+
+static LStr make_str(int32_t ndim, const int64_t *s)
+{
+    LStr r;
+    for (int d = 0; d < 3; d++) r.s[d] = d < ndim ? s[d] : 0;
+    return r;
+}
+
+// 0: nothing to do; -1: a plane too large for the 32-bit index
+static int grid_of(const LGeom &g, dim3 &grid)
+{
+    if (g.shape[0] * g.shape[1] * g.shape[2] == 0) return 0;
+    const int64_t inner = g.shape[g.ax[1]] * g.shape[g.ax[2]];
+    if (inner >= (1ll << 31)) return -1;
+    const int64_t n0 = g.shape[g.ax[0]];
+    grid = dim3((unsigned)((inner + 255) / 256), (unsigned)(n0 < 65535 ? n0 : 65535));
+    return 1;
+}
+
+}  // namespace pmx
+
+using namespace pmx;
+
+extern "C" int pmx_apply_ktable(const pmx_ktable *t, int32_t ndim, int32_t elsize, const void *in,
+                                const int64_t *in_strides, void *out, const int64_t *out_strides,
+                                const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                                const double *boxsize, void *stream)
+{
+    PMX_REQUIRE(t && ndim >= 1 && ndim <= 3 && in && out && in_strides && out_strides && shape, PMX_EINVAL,
+                "bad arguments");
+    PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
+    PMX_REQUIRE(t->n >= 2 && t->n <= PMX_KTABLE_MAX, PMX_EUNSUPPORTED, "table of 2 .. PMX_KTABLE_MAX entries");
+    PMX_REQUIRE(t->x && t->y, PMX_EINVAL, "table pointers");
+    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
+    dim3 grid;
+    const int r = grid_of(g, grid);
+    PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
+    if (r == 0) return PMX_OK;
+    const LStr is = make_str(ndim, in_strides), os = make_str(ndim, out_strides);
+    hipStream_t st = (hipStream_t)stream;
+    const char *a = (const char *)in;
+    char *b = (char *)out;
+    if (elsize == 8) {
+        if (t->loglog) ktable_kernel<double, true><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
+        else ktable_kernel<double, false><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
+    } else {
+        if (t->loglog) ktable_kernel<float, true><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
+        else ktable_kernel<float, false><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
+    }
+    PMX_HIP_CHECK(hipGetLastError());
+    return PMX_OK;
+}
+
+extern "C" int pmx_lpt_hessian(int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides, int32_t nout,
+                               const int32_t *pairs, void *const *out, const int64_t *out_strides,
+                               const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                               const double *boxsize, void *stream)
+{
+    PMX_REQUIRE(ndim >= 1 && ndim <= 3 && in && in_strides && pairs && out && out_strides && shape, PMX_EINVAL,
+                "bad arguments");
+    PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
+    PMX_REQUIRE(nout >= 1 && nout <= 3, PMX_EINVAL, "1 .. 3 outputs");
+    HOut o;
+    for (int p = 0; p < 3; p++) {
+        const bool on = p < nout;
+        o.p[p] = on ? (char *)out[p] : nullptr;
+        o.s[p] = make_str(ndim, on ? out_strides + 3 * p : in_strides);
+        o.i[p] = on ? pairs[2 * p] : 0;
+        o.j[p] = on ? pairs[2 * p + 1] : 0;
+        PMX_REQUIRE(!on || (o.p[p] && o.i[p] >= 0 && o.i[p] < ndim && o.j[p] >= 0 && o.j[p] < ndim), PMX_EINVAL,
+                    "output pointer or pair out of range");
+    }
+    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, in_strides);
+    dim3 grid;
+    const int r = grid_of(g, grid);
+    PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
+    if (r == 0) return PMX_OK;
+    const LStr is = make_str(ndim, in_strides);
+    hipStream_t st = (hipStream_t)stream;
+    const char *a = (const char *)in;
+    if (elsize == 8) {
+        if (nout == 1) hessian_kernel<double, 1><<<grid, 256, 0, st>>>(g, a, is, o);
+        else if (nout == 2) hessian_kernel<double, 2><<<grid, 256, 0, st>>>(g, a, is, o);
+        else hessian_kernel<double, 3><<<grid, 256, 0, st>>>(g, a, is, o);
+    } else {
+        if (nout == 1) hessian_kernel<float, 1><<<grid, 256, 0, st>>>(g, a, is, o);
+        else if (nout == 2) hessian_kernel<float, 2><<<grid, 256, 0, st>>>(g, a, is, o);
+        else hessian_kernel<float, 3><<<grid, 256, 0, st>>>(g, a, is, o);
+    }
+    PMX_HIP_CHECK(hipGetLastError());
+    return PMX_OK;
+}
+
+extern "C" int pmx_lpt2_source(int32_t ndim, int32_t elsize, const void *const *in, const int64_t *in_strides,
+                               void *out, const int64_t *out_strides, const int64_t *shape, double scale, void *stream)
+{
+    PMX_REQUIRE((ndim == 2 || ndim == 3) && in && in_strides && out && out_strides && shape, PMX_EINVAL,
+                "bad arguments (ndim 2 or 3)");
+    PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
+    const int nin = ndim == 2 ? 3 : 6;
+    SIn a;
+    for (int q = 0; q < 6; q++) {
+        const bool on = q < nin;
+        a.p[q] = on ? (const char *)in[q] : nullptr;
+        a.s[q] = make_str(ndim, on ? in_strides + 3 * q : out_strides);
+        PMX_REQUIRE(!on || a.p[q], PMX_EINVAL, "input pointer");
+    }
+    LGeom g = make_geom(ndim, shape, nullptr, nullptr, nullptr, out_strides);
+    dim3 grid;
+    const int r = grid_of(g, grid);
+    PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 elements");
+    if (r == 0) return PMX_OK;
+    const LStr os = make_str(ndim, out_strides);
+    hipStream_t st = (hipStream_t)stream;
+    char *b = (char *)out;
+    if (elsize == 8) {
+        if (ndim == 2) lpt2_source_kernel<double, 2><<<grid, 256, 0, st>>>(g, a, b, os, scale);
+        else lpt2_source_kernel<double, 3><<<grid, 256, 0, st>>>(g, a, b, os, scale);
+    } else {
+        if (ndim == 2) lpt2_source_kernel<float, 2><<<grid, 256, 0, st>>>(g, a, b, os, scale);
+        else lpt2_source_kernel<float, 3><<<grid, 256, 0, st>>>(g, a, b, os, scale);
+    }
+    PMX_HIP_CHECK(hipGetLastError());
+    return PMX_OK;
+}

@@ -121,3 +121,97 @@ class Transfer(object):
                 D = 1.0 / Cc * 1 / 6.0 * (8 * xp_sin(w) - xp_sin(2 * w))
             r = 1j * (r * D)
         return r * v
+
+
+class Tabulated(Transfer):
+    """A transfer function tabulated in |k| (an extension; the reference's callers evaluate one with numpy.interp
+    inside Field.apply, examples/nbody.py:245-282):
+
+        T(|k|) = amplitude * interp(|k|),    |k| = sqrt((k_0^2 + k_1^2) + k_2^2)
+
+    loglog=False: interp is ``numpy.interp(|k|, k, t, left, right)``.  loglog=True: it is
+    ``exp(numpy.interp(log|k|, log k, log t))`` for k[0] <= |k| <= k[-1], `left` below and `right` above (|k| = 0
+    gives `left`).  k: 2 .. PMX_KTABLE_MAX strictly increasing finite values (positive when loglog), t: as many finite
+    values (positive when loglog).
+
+    One kernel over the complex field (csrc/pmx_lpt.hip: ktable_kernel, a binary search of the table in device
+    memory, started from a closed-form guess when the table is uniform in k, or in log k for loglog); it is not fused into c2r, so ``c2r(transfer=Tabulated(...))`` applies it as a kernel of its own.  Like
+    every Transfer it is also a ``func(k, v)`` callable evaluated with array operators on the host or device.
+
+        delta_k = pm.generate_whitenoise(seed, unitary=True).apply(Tabulated(k, (P / V) ** 0.5, loglog=True))
+    """
+
+    def __init__(self, k, t, loglog=False, amplitude=1.0, left=0.0, right=0.0):
+        Transfer.__init__(self, amplitude=amplitude)
+        k = numpy.array(k, dtype='f8')
+        t = numpy.array(t, dtype='f8')
+        if k.ndim != 1 or t.ndim != 1 or len(k) != len(t):
+            raise ValueError('k and t must be 1-d arrays of the same length')
+        if len(k) < 2 or len(k) > _abi.PMX_KTABLE_MAX:
+            raise ValueError('a table of 2 .. PMX_KTABLE_MAX = %d entries, not %d' % (_abi.PMX_KTABLE_MAX, len(k)))
+        if not (numpy.isfinite(k).all() and numpy.isfinite(t).all()):
+            raise ValueError('k and t must be finite')
+        if not (numpy.diff(k) > 0).all():
+            raise ValueError('k must be strictly increasing')
+        self.loglog = bool(loglog)
+        if self.loglog and not ((k > 0).all() and (t > 0).all()):
+            raise ValueError('loglog tables need positive k and t')
+        self.left, self.right = float(left), float(right)
+        if not (numpy.isfinite(self.amplitude) and numpy.isfinite(self.left) and numpy.isfinite(self.right)):
+            raise ValueError('amplitude, left and right must be finite')
+        self.k, self.t = k, t
+        self._x, self._y = (numpy.log(k), numpy.log(t)) if self.loglog else (k, t)
+        self._dev = {}
+
+    def fusable(self):
+        return False
+
+    def _table(self, device):
+        """the device copy of the table (x, y as float64) and its pmx_ktable"""
+        got = self._dev.get(device)
+        if got is None:
+            x = torch.from_numpy(self._x).to(device)
+            y = torch.from_numpy(self._y).to(device)
+            s = _abi.KTable()
+            s.n, s.loglog, s.amplitude = len(self._x), int(self.loglog), self.amplitude
+            s.left, s.right, s.kmin, s.kmax = self.left, self.right, float(self.k[0]), float(self.k[-1])
+            # a table uniform in x (k, or log k): the kernel's search starts from a closed-form guess
+            step = numpy.diff(self._x)
+            if numpy.abs(step - step.mean()).max() <= 1e-6 * step.mean():
+                s.inv_step = 1.0 / step.mean()
+            s.x, s.y = x.data_ptr(), y.data_ptr()
+            got = self._dev[device] = (x, y, s)
+        return got
+
+    def _launch(self, field, outv):
+        be = backend.get()
+        v = field.value
+        if v.numel() == 0:
+            return
+        x, y, s = self._table(be.device)
+        be.apply_ktable(s, v, outv, field.start, field.Nmesh, field.BoxSize)
+
+    def interp(self, kmag):
+        """interp(|k|) of the class docstring on a numpy array"""
+        kmag = numpy.asarray(kmag, dtype='f8')
+        if not self.loglog:
+            return numpy.interp(kmag, self.k, self.t, left=self.left, right=self.right)
+        inside = (kmag >= self.k[0]) & (kmag <= self.k[-1])
+        with numpy.errstate(divide='ignore', invalid='ignore'):
+            u = numpy.log(numpy.where(inside, kmag, self.k[0]))
+        return numpy.where(inside, numpy.exp(numpy.interp(u, self._x, self._y)),
+                           numpy.where(kmag < self.k[0], self.left, self.right))
+
+    def __call__(self, k, v):
+        """ the same transfer as a reference-style filter func(k, v), kind='wavenumber' (evaluated on the host) """
+        from ._devarr import DevArr
+        k2 = 0
+        for ki in k:
+            ki = ki.cpu().numpy() if isinstance(ki, (torch.Tensor, DevArr)) else numpy.asarray(ki)
+            k2 = k2 + ki * ki
+        f = self.amplitude * self.interp(numpy.sqrt(k2))
+        if isinstance(v, DevArr):
+            return DevArr(v.t * torch.from_numpy(numpy.ascontiguousarray(f)).to(v.t.device))
+        if isinstance(v, torch.Tensor):
+            return v * torch.from_numpy(numpy.ascontiguousarray(f)).to(v.device)
+        return f * v
