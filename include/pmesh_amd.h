@@ -568,6 +568,43 @@ int pmx_lpt_hessian(int32_t ndim, int32_t elsize, const void *in, const int64_t 
 int pmx_lpt2_source(int32_t ndim, int32_t elsize, const void *const *in, const int64_t *in_strides, void *out,
                     const int64_t *out_strides, const int64_t *shape, double scale, void *stream);
 
+/* ---- gradients of second-order LPT (the reference's pmesh/abopt.py chains, per component, the vjp of apply_transfer
+ * with the conjugated factor and the c2r / r2c vjps: pmesh_amd.lpt.lpt_vjp / lpt_jvp) ---------------------------------
+ * Geometry as above. */
+
+/* The adjoint contraction over complex blocks, replacing abopt.py's transfer vjp (x * conj(tf(k))) summed over
+ * components: out[m] = (accumulate ? out[m] : 0) + sum_c f_c(k) in[c][m] for c = 0, 1, .., nin - 1 in that order
+ * (nin 1..6), in double, where for (a, b) = (factors[2 c], factors[2 c + 1])
+ *   f_c = k_a k_b / k^2      (b >= 0: a Hessian factor, real)
+ *   f_c = -i k_a / k^2       (b < 0: the conjugate of the gradient factor i k_a / k^2 of Transfer.dx1)
+ * and every f_c is 0 at k = 0.  in (host array of device pointers), in_strides (3 per input) and factors are host
+ * arrays; out may equal in[0] (same strides). */
+int pmx_lpt_contract(int32_t ndim, int32_t elsize, int32_t nin, const void *const *in, const int64_t *in_strides,
+                     const int32_t *factors, int32_t accumulate, void *out, const int64_t *out_strides,
+                     const int64_t *shape, const int64_t *start, const int64_t *nmesh, const double *boxsize,
+                     void *stream);
+
+/* The vjp of pmx_lpt2_source with respect to its inputs, replacing abopt.py's products of the cotangent with the
+ * partial derivatives of the source: with a = scale * g[m] (g a real block) and phi the 3 (2-d) or 6 (3-d) components
+ * in[] in the order of pmx_lpt2_source, writes in double
+ *   2-d: out[0] = a phi_11, out[1] = a phi_00, out[2] = a (-2 phi_01)
+ *   3-d: out[0] = a (phi_11 + phi_22), out[1] = a (phi_22 + phi_00), out[2] = a (phi_00 + phi_11),
+ *        out[3] = a (-2 phi_01), out[4] = a (-2 phi_02), out[5] = a (-2 phi_12).
+ * Every input of an element is read before any output of it is written: out[p] may equal in[p] (same strides). */
+int pmx_lpt2_source_vjp(int32_t ndim, int32_t elsize, const void *g, const int64_t *g_strides, const void *const *in,
+                        const int64_t *in_strides, void *const *out, const int64_t *out_strides, const int64_t *shape,
+                        double scale, void *stream);
+
+/* The jvp of pmx_lpt2_source, replacing abopt.py's product rule over real fields: with phi = in[] and phi' = tangent[]
+ * (the same order of components), writes in double and in this order of operations
+ *   out = scale * ((phi_00 phi'_11 + phi'_00 phi_11) - 2 (phi_01 phi'_01))                                  (2-d)
+ *   s = (phi_00 phi'_11 + phi'_00 phi_11) + (phi_11 phi'_22 + phi'_11 phi_22);  s = s + (phi_22 phi'_00 + phi'_22 phi_00);
+ *   s = s - 2 (phi_01 phi'_01);  s = s - 2 (phi_02 phi'_02);  s = s - 2 (phi_12 phi'_12);  out = scale * s     (3-d)
+ * out may equal tangent[0] (same strides); ndim 2 or 3. */
+int pmx_lpt2_source_jvp(int32_t ndim, int32_t elsize, const void *const *in, const int64_t *in_strides,
+                        const void *const *tangent, const int64_t *tangent_strides, void *out,
+                        const int64_t *out_strides, const int64_t *shape, double scale, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

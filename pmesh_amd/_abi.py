@@ -191,6 +191,12 @@ DEVICE_ONLY = {
     'lpt_hessian': (C.c_int, [_i32, _i32, _vp, _P(_i64), _i32, _P(C.c_int32), _P(_vp), _P(_i64), _P(_i64), _P(_i64),
                               _P(_i64), _P(_f64), _vp]),
     'lpt2_source': (C.c_int, [_i32, _i32, _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _f64, _vp]),
+    'lpt_contract': (C.c_int, [_i32, _i32, _i32, _P(_vp), _P(_i64), _P(C.c_int32), _i32, _vp, _P(_i64), _P(_i64),
+                               _P(_i64), _P(_i64), _P(_f64), _vp]),
+    'lpt2_source_vjp': (C.c_int, [_i32, _i32, _vp, _P(_i64), _P(_vp), _P(_i64), _P(_vp), _P(_i64), _P(_i64), _f64,
+                                  _vp]),
+    'lpt2_source_jvp': (C.c_int, [_i32, _i32, _P(_vp), _P(_i64), _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _f64,
+                                  _vp]),
 }
 
 

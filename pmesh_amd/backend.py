@@ -249,6 +249,40 @@ class HipBackend(object):
                   _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3), float(scale),
                   self.stream())
 
+    @staticmethod
+    def _ptr_set(ts, es):
+        ptrs = (C.c_void_p * len(ts))(*[a.data_ptr() for a in ts])
+        strides = _abi.i64arr([s * es for a in ts for s in (list(a.stride()) + [0] * 3)[:3]])
+        return ptrs, strides
+
+    def lpt_contract(self, ins, factors, out, accumulate, start, nmesh, boxsize):
+        """out = (accumulate ? out : 0) + sum_c f_c(k) ins[c] over local complex blocks, 1-6 inputs; factors[c] = (i, j)
+        for k_i k_j / k^2 or (d, -1) for -i k_d / k^2 (pmx_lpt_contract); out may be ins[0]"""
+        es = out.element_size()
+        ptrs, strides = self._ptr_set(ins, es)
+        flat = (C.c_int32 * (2 * len(ins)))(*[int(x) for f in factors for x in f])
+        self.call('lpt_contract', out.dim(), es // 2, len(ins), ptrs, strides, flat, int(bool(accumulate)),
+                  out.data_ptr(), _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3),
+                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+
+    def lpt2_source_vjp(self, g, ins, outs, scale):
+        """outs[p] = scale * g * dS / d ins[p] over real blocks, components in the order of lpt2_source
+        (pmx_lpt2_source_vjp); outs[p] may be ins[p]"""
+        es = g.element_size()
+        ip, istr = self._ptr_set(ins, es)
+        op, ostr = self._ptr_set(outs, es)
+        self.call('lpt2_source_vjp', g.dim(), es, g.data_ptr(), _abi.i64arr([s * es for s in g.stride()], 3), ip,
+                  istr, op, ostr, _abi.i64arr(g.shape, 3), float(scale), self.stream())
+
+    def lpt2_source_jvp(self, ins, tangents, out, scale):
+        """out = scale * dS(ins; tangents) over real blocks (pmx_lpt2_source_jvp); out may be tangents[0]"""
+        es = out.element_size()
+        ip, istr = self._ptr_set(ins, es)
+        tp, tstr = self._ptr_set(tangents, es)
+        self.call('lpt2_source_jvp', out.dim(), es, ip, istr, tp, tstr, out.data_ptr(),
+                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3), float(scale),
+                  self.stream())
+
 
 _current = None
 
