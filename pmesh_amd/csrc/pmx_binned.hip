@@ -2246,6 +2246,14 @@ __device__ __forceinline__ void tile_gather_lean(const pmx_painter &p, const Bin
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) row[u] = pos_row<PE>(pos, (int64_t)id[u]);
+        if constexpr (ENT) {
+            // (opaque: the rows of BOTH slots are loaded here, in front of the masks' branches.  Left alone the compiler
+            // sinks the first slot's loads behind its mask test — mask, branch, block number, position: three memory
+            // round trips in a row per trip where the list form has two, and its two slots side by side.  That, not the
+            // idle lanes, is what the entry form's readout lost to the list on rows with full masks: DESIGN.md §5.1)
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) asm volatile("" : "+v"(row[u].x[0]), "+v"(row[u].x[1]), "+v"(row[u].x[2]));
+        }
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             if (!ok[u]) continue;
