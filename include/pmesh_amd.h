@@ -521,6 +521,34 @@ int pmx_power_project(const pmx_power *p, int32_t ndim, int32_t elsize, const vo
                       const int64_t *nmesh, const double *boxsize, const double *kedges, const double *muedges,
                       double *acc, void *stream);
 
+/* The adjoint of pmx_power_project with respect to the fields (pmesh_amd.power.power_spectrum_vjp): reads a (and b)
+ * once and writes grad_a (and grad_b; both NULL for the auto spectrum) once, blocks of the shape and element size of a
+ * with their own byte strides, not aliasing a or b.  Arguments, limits and per-mode quantities are those of
+ * pmx_power_project: per stored mode m its k bin j, mu, its mu bin mubin(mu), D_m = prod_d sinc(pi s_d / N_d)^deconv_pow,
+ * h_m = 1 when the mode also stands for its conjugate (hermitian = 1, last-axis index neither 0 nor N/2), else 0, and
+ * w_m = 1 + h_m.
+ *
+ * coef is a DEVICE array of float64 that the caller builds from the cotangents v_* of the power-like columns and the
+ * (global) counts; its layout is that of acc without the count, |k| and mu columns (C = 2 + 2 npoles doubles per k
+ * bin, then 2 per (k, mu) cell):
+ *   coef[j*C + {0, 1}]                         Re, Im of c1[j]    = v_power[j] / modes[j]
+ *   coef[j*C + 2 + 2p + {0, 1}]                Re, Im of cp[p][j] = (2 ell_p + 1) v_poles[ell_p][j] / modes[j]
+ *   coef[nk*C + (j*nmu + m)*2 + {0, 1}]        Re, Im of c2[j, m] = v_power2d[j, m] / modes2d[j, m]
+ * each 0 where the count is 0.  With
+ *   F_m(mu) = c1[j] + sum_p L_ell_p(mu) cp[p][j] + c2[j, mubin(mu)]     (the last term 0 when mu is outside muedges)
+ *   q_m     = (V / D_m) (conj(F_m(mu_m)) + h_m F_m(-mu_m)),             L_ell(-mu) = (-1)^ell L_ell(mu)
+ * the kernel writes, in double,
+ *   grad_a = conj(q) b / w,   grad_b = q a / w        (cross)
+ *   grad_a = 2 Re(q) a / w                            (auto)
+ * and 0 for a mode outside kedges: for L = Re sum conj(v) P over every power-like column, Re sum_m w_m conj(u_m)
+ * grad_m is the derivative of L along u.  A tile keeps a window of coefficient rows in LDS as pmx_power_project keeps
+ * its window of sums; there are no atomics and the result is deterministic. */
+int pmx_power_vjp(const pmx_power *p, int32_t ndim, int32_t elsize, const void *a, const int64_t *a_strides,
+                  const void *b, const int64_t *b_strides, void *grad_a, const int64_t *grad_a_strides, void *grad_b,
+                  const int64_t *grad_b_strides, const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                  const double *boxsize, const double *kedges, const double *muedges, const double *coef,
+                  void *stream);
+
 /* ---- initial conditions: tabulated transfers and second-order LPT (the reference's examples/nbody.py:245-282 builds
  * its linear field with a tabulated P(k) through Field.apply; nbody/genic.py:121-166 the 2LPT displacements) --------
  * Geometry as in pmx_apply_transfer: a local block of logical shape[0..ndim) at global index start[], byte strides
@@ -551,6 +579,33 @@ typedef struct pmx_ktable {
 int pmx_apply_ktable(const pmx_ktable *t, int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides,
                      void *out, const int64_t *out_strides, const int64_t *shape, const int64_t *start,
                      const int64_t *nmesh, const double *boxsize, void *stream);
+
+/* The adjoint of pmx_apply_ktable with respect to the table values (pmesh_amd.transfer.Tabulated.apply_vjp): reads the
+ * complex blocks in and v once and ADDS into grad, a device array of n float64 that the caller has zeroed (and sums
+ * over the ranks),
+ *   grad[i] += sum_m w_m Re(conj(v_m) in_m) e_i(|k_m|),
+ * with w_m = 2 when hermitian = 1 and the mode's last-axis index is neither 0 nor N/2 (the rule of pmx_power_project),
+ * else 1, and e_i the derivative of the interpolant with respect to y[i] (loglog = 0) or to ln-space y[i] times f
+ * (loglog = 1), following numpy.interp's rules as stated for pmx_apply_ktable: for kmin <= |k| <= kmax and u = |k| or
+ * ln |k|,
+ *   u <= x[0]:      e_0 = E;   u >= x[n - 1]:  e_{n-1} = E;
+ *   x[j] < u < x[j + 1] (the same search):  e_j = (1 - f) E, e_{j+1} = f E,  f = (u - x[j]) / (x[j + 1] - x[j]),
+ * E = 1 (loglog = 0) or exp(g(u)) (loglog = 1), every other e_i = 0, and all e_i = 0 for |k| < kmin or |k| > kmax
+ * (left and right are constants).  The caller multiplies by the amplitude and, for loglog, divides grad[i] by t[i]
+ * (d ln t_i = d t_i / t_i).  A workgroup sums into an LDS copy of grad (n doubles) and adds its non-zero entries with
+ * float atomics once: the last bits may differ from run to run. */
+int pmx_ktable_vjp(const pmx_ktable *t, int32_t hermitian, int32_t ndim, int32_t elsize, const void *in,
+                   const int64_t *in_strides, const void *v, const int64_t *v_strides, const int64_t *shape,
+                   const int64_t *start, const int64_t *nmesh, const double *boxsize, double *grad, void *stream);
+
+/* The tangent of pmx_apply_ktable along the table values (pmesh_amd.transfer.Tabulated.apply_jvp): dy is a device
+ * array of n float64, the tangent of y (for loglog = 1 of ln t: dt / t).  out[m] = T'(|k|) in[m], in may equal out,
+ *   T'(|k|) = amplitude * g'(u)             (loglog = 0)
+ *             amplitude * exp(g(u)) g'(u)   (loglog = 1)      for kmin <= |k| <= kmax, 0 outside,
+ * with g as in pmx_apply_ktable and g' the same interpolation (same j, same clamping) of dy over x. */
+int pmx_apply_ktable_jvp(const pmx_ktable *t, const double *dy, int32_t ndim, int32_t elsize, const void *in,
+                         const int64_t *in_strides, void *out, const int64_t *out_strides, const int64_t *shape,
+                         const int64_t *start, const int64_t *nmesh, const double *boxsize, void *stream);
 
 /* Reads the complex block `in` once and writes, for each of nout (1..3) pairs (i, j) = (pairs[2 p], pairs[2 p + 1]),
  * out[p][m] = (k_i k_j / k^2) * in[m] (0 at k = 0) with byte strides out_strides[3 p .. 3 p + 3).  pairs, out and

@@ -186,8 +186,14 @@ DEVICE_ONLY = {
     'slab_unpack': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _P(_i64), _i32, _i32, _vp]),
     'power_project': (C.c_int, [_P(Power), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
                                 _P(_f64), _vp, _vp, _vp, _vp]),
+    'power_vjp': (C.c_int, [_P(Power), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _vp, _P(_i64), _vp, _P(_i64), _P(_i64),
+                            _P(_i64), _P(_i64), _P(_f64), _vp, _vp, _vp, _vp]),
     'apply_ktable': (C.c_int, [_P(KTable), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
                                _P(_f64), _vp]),
+    'ktable_vjp': (C.c_int, [_P(KTable), _i32, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
+                             _P(_f64), _vp, _vp]),
+    'apply_ktable_jvp': (C.c_int, [_P(KTable), _vp, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64),
+                                   _P(_i64), _P(_f64), _vp]),
     'lpt_hessian': (C.c_int, [_i32, _i32, _vp, _P(_i64), _i32, _P(C.c_int32), _P(_vp), _P(_i64), _P(_i64), _P(_i64),
                               _P(_i64), _P(_f64), _vp]),
     'lpt2_source': (C.c_int, [_i32, _i32, _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _f64, _vp]),

@@ -218,6 +218,23 @@ class HipBackend(object):
                   kedges.data_ptr(), muedges.data_ptr() if muedges is not None else None, acc.data_ptr(),
                   self.stream())
 
+    def power_vjp(self, params, a, b, grad_a, grad_b, start, nmesh, boxsize, kedges, muedges, coef):
+        """grad_a (and grad_b; b, grad_b None: the auto spectrum) = the adjoint of power_project for the coefficient
+        table `coef`, a float64 device vector (layout: include/pmesh_amd.h, pmx_power_vjp)"""
+        if a.numel() == 0:
+            return
+        es = a.element_size()
+
+        def strides(t):
+            return _abi.i64arr([s * es for s in t.stride()], 3) if t is not None else None
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        self.call('power_vjp', C.byref(params), a.dim(), es // 2, ptr(a), strides(a), ptr(b), strides(b), ptr(grad_a),
+                  strides(grad_a), ptr(grad_b), strides(grad_b), _abi.i64arr(a.shape, 3), _abi.i64arr(start, 3),
+                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), kedges.data_ptr(),
+                  muedges.data_ptr() if muedges is not None else None, coef.data_ptr(), self.stream())
+
     # -- initial conditions: tabulated transfer, 2LPT ----------------------
     def apply_ktable(self, table, v, out, start, nmesh, boxsize):
         """out = T(|k|) v over the local complex block v (pmx_apply_ktable; `table` a _abi.KTable whose x / y are
@@ -226,6 +243,24 @@ class HipBackend(object):
         self.call('apply_ktable', C.byref(table), v.dim(), es // 2, v.data_ptr(), _abi.i64arr([s * es for s in v.stride()], 3),
                   out.data_ptr(), _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(v.shape, 3),
                   _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+
+    def ktable_vjp(self, table, hermitian, field, v, start, nmesh, boxsize, grad):
+        """grad[i] += sum_m w_m Re(conj(v_m) field_m) e_i(|k_m|) over the local complex blocks (pmx_ktable_vjp; grad:
+        float64 device vector of table.n entries)"""
+        es = field.element_size()
+        self.call('ktable_vjp', C.byref(table), int(bool(hermitian)), field.dim(), es // 2, field.data_ptr(),
+                  _abi.i64arr([s * es for s in field.stride()], 3), v.data_ptr(),
+                  _abi.i64arr([s * es for s in v.stride()], 3), _abi.i64arr(field.shape, 3), _abi.i64arr(start, 3),
+                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), grad.data_ptr(), self.stream())
+
+    def apply_ktable_jvp(self, table, dy, v, out, start, nmesh, boxsize):
+        """out = T'(|k|) v, the tangent of apply_ktable along the table values (pmx_apply_ktable_jvp; dy: float64
+        device vector of table.n entries); out may be v"""
+        es = v.element_size()
+        self.call('apply_ktable_jvp', C.byref(table), dy.data_ptr(), v.dim(), es // 2, v.data_ptr(),
+                  _abi.i64arr([s * es for s in v.stride()], 3), out.data_ptr(),
+                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3),
+                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
 
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v

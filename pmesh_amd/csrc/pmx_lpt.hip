@@ -28,36 +28,6 @@ struct SIn {
     LStr s[6];
 };
 
-// numpy.interp(u, x, y) with its end values outside [x[0], x[n-1]]: binary search for x[j] <= u < x[j + 1], started
-// from the closed-form guess j = (u - x[0]) * inv_step of a uniform table (inv_step > 0), which narrows the search to
-// one side of the guess and ends it at once when the guess holds
-__device__ __forceinline__ double table_interp(const double *x, const double *y, int n, double inv_step, double u)
-{
-    const double x0 = x[0];
-    if (u <= x0) return y[0];
-    if (u >= x[n - 1]) return y[n - 1];
-    int lo = 0, hi = n - 1;     // x[lo] <= u < x[hi]
-    if (inv_step > 0) {
-        const double t = (u - x0) * inv_step;
-        const int g = t < 0 ? 0 : (t > n - 2 ? n - 2 : (int)t);
-        if (x[g] <= u) {
-            lo = g;
-            if (u < x[g + 1]) hi = g + 1;
-        } else {
-            hi = g;
-        }
-    }
-    while (hi - lo > 1) {
-        const int m = (lo + hi) >> 1;
-        if (x[m] <= u) lo = m;
-        else hi = m;
-    }
-    const double xl = x[lo], yl = y[lo];
-    if (xl == u) return yl;
-    const double s = (y[lo + 1] - yl) / (x[lo + 1] - xl);
-    return s * (u - xl) + yl;
-}
-
 template <typename T, bool LOG>
 __global__ void __launch_bounds__(256) ktable_kernel(pmx_ktable t, LGeom g, const char *in, LStr is, char *out, LStr os)
 {

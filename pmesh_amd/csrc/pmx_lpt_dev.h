@@ -1,7 +1,8 @@
-// pmx_lpt_dev.h — what the streaming kernels over spectra and real blocks of pmx_lpt.hip and pmx_lpt_grad.hip share:
-// the block geometry in logical order with its memory-order walk (PMX_LPT_LOOP), the wavevector of an element from its
-// index (pmx_common.h: wavenumber, the roundings of transfer_kernel), complex loads and stores of f4 / f8 storage into
-// double, and the host side that builds the geometry and the launch grid.
+// pmx_lpt_dev.h — what the streaming kernels over spectra and real blocks of pmx_lpt.hip, pmx_lpt_grad.hip and
+// pmx_ktable_grad.hip share: the block geometry in logical order with its memory-order walk (PMX_LPT_LOOP), the
+// wavevector of an element from its index (pmx_common.h: wavenumber, the roundings of transfer_kernel), complex loads
+// and stores of f4 / f8 storage into double, the search and interpolation of a pmx_ktable, and the host side that
+// builds the geometry and the launch grid.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -75,6 +76,42 @@ template <> struct CLoad<float> {
         *(float2 *)p = make_float2((float)re, (float)im);
     }
 };
+
+// j with x[j] <= u < x[j + 1] for x[0] < u < x[n - 1] (the table search of pmx_apply_ktable and its gradients): binary
+// search, started from the closed-form guess j = (u - x[0]) * inv_step of a uniform table (inv_step > 0), which
+// narrows the search to one side of the guess and ends it at once when the guess holds
+__device__ __forceinline__ int table_find(const double *x, int n, double inv_step, double u)
+{
+    int lo = 0, hi = n - 1;     // x[lo] <= u < x[hi]
+    if (inv_step > 0) {
+        const double t = (u - x[0]) * inv_step;
+        const int g = t < 0 ? 0 : (t > n - 2 ? n - 2 : (int)t);
+        if (x[g] <= u) {
+            lo = g;
+            if (u < x[g + 1]) hi = g + 1;
+        } else {
+            hi = g;
+        }
+    }
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (x[m] <= u) lo = m;
+        else hi = m;
+    }
+    return lo;
+}
+
+// numpy.interp(u, x, y) with its end values outside [x[0], x[n-1]]
+__device__ __forceinline__ double table_interp(const double *x, const double *y, int n, double inv_step, double u)
+{
+    if (u <= x[0]) return y[0];
+    if (u >= x[n - 1]) return y[n - 1];
+    const int lo = table_find(x, n, inv_step, u);
+    const double xl = x[lo], yl = y[lo];
+    if (xl == u) return yl;
+    const double s = (y[lo + 1] - yl) / (x[lo + 1] - xl);
+    return s * (u - xl) + yl;
+}
 
 // the block geometry, axes ordered by decreasing |stride| of `order` (the rule of pmx_apply_transfer)
 static LGeom make_geom(int32_t ndim, const int64_t *shape, const int64_t *start, const int64_t *nmesh,

@@ -27,6 +27,24 @@ Gradients (lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp) follow the conventi
 a cotangent of a ComplexField is returned in the form RealField.c2r_vjp returns (before decompress_vjp), so that
 Re(u.cdot(grad)) is the derivative along u; the adjoint chain runs paint -> r2c -> conj(i k_d / k^2) for the readouts
 of gradients, r2c_vjp -> dS/dphi -> r2c -> k_i k_j / k^2 for the source (csrc/pmx_lpt_grad.hip).
+
+The backward chain of a field-level fit of the table values t (band powers, transfer-function nodes) to a measured
+spectrum, every step on the device:
+
+    w = pm.generate_whitenoise(seed, unitary=True)
+    tab = Tabulated(k, t, loglog=True)
+    delta_k = w.apply(tab)
+    dx1, dx2 = lpt(delta_k, q)
+    x = q + D1 * dx1 + D2 * dx2
+    c = pm.paint(x).r2c()
+    res = power_spectrum(c, kedges, poles=(0, 2))                     # chi^2 = sum_ell sum_j (Re P_ell - target_ell)^2
+    v = {ell: 2 * (res.poles[ell].real - target[ell]) for ell in (0, 2)}
+    grad_c = power_spectrum_vjp(c, kedges, v_poles=v, poles=(0, 2), result=res)
+    grad_x, _ = pm.paint_vjp(grad_c.r2c_vjp(), x, out_mass=False)
+    grad_delta, _ = lpt_vjp(delta_k, q, D1 * grad_x, D2 * grad_x)
+    grad_w, grad_t = tab.apply_vjp(w, grad_delta)                     # d chi^2 / d t, summed over the ranks
+
+(pmesh_amd.power.power_spectrum_vjp, transfer.Tabulated.apply_vjp; their tangents power_spectrum_jvp and apply_jvp).
 """
 import numpy
 import torch

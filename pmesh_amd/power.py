@@ -71,6 +71,97 @@ def _complex(field):
     return field
 
 
+class _Plan(object):
+    """the checked arguments of one spectrum: the fields, the edges, the multipole orders and the pmx_power struct"""
+
+    def __init__(self, field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex):
+        a = convert(field)
+        pm = a.pm
+        ndim = len(pm.Nmesh)
+        if ndim > _abi.PMX_MAXDIM:
+            raise NotImplementedError('power spectra of meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
+        b = None
+        if other is not None:
+            b = convert(other)
+            if b.pm is not pm and (tuple(b.pm.Nmesh) != tuple(pm.Nmesh) or tuple(b.pm.BoxSize) != tuple(pm.BoxSize)
+                                   or b.pm.comm is not pm.comm):
+                raise ValueError('the two fields belong to different meshes')
+            _same_layout(a, b)
+        if a.value.dtype not in (torch.complex64, torch.complex128):
+            raise ValueError('power_spectrum measures complex64 or complex128 fields')
+
+        ke = _edges('kedges', kedges)
+        if len(ke) - 1 > _abi.PMX_POWER_MAX_KBINS:
+            raise ValueError('%d k bins: more than PMX_POWER_MAX_KBINS = %d' % (len(ke) - 1, _abi.PMX_POWER_MAX_KBINS))
+        me = None
+        if muedges is not None:
+            me = _edges('muedges', muedges, -1.0, 1.0)
+            if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
+                raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d'
+                                 % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
+        ells = [int(ell) for ell in poles]
+        if len(ells) > _abi.PMX_POWER_MAX_POLES:
+            raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
+        if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
+            raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
+        if int(deconv_pow) != deconv_pow or deconv_pow < 0:
+            raise ValueError('deconv_pow must be a non-negative integer')
+        if los is None:
+            los = numpy.zeros(ndim)
+            los[-1] = 1.0
+        los = numpy.array(los, dtype='f8').reshape(-1)
+        norm = numpy.sqrt((los ** 2).sum())
+        if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
+            raise ValueError('los must be a nonzero vector of %d components' % ndim)
+        los = los / norm
+
+        p = _abi.Power()
+        p.nk = len(ke) - 1
+        p.nmu = 0 if me is None else len(me) - 1
+        p.npoles = len(ells)
+        for i, ell in enumerate(ells):
+            p.poles[i] = ell
+        p.hermitian = int(bool(a.compressed))
+        p.deconv_pow = int(deconv_pow)
+        p.volume = float(numpy.prod(pm.BoxSize))
+        for d in range(ndim):
+            p.los[d] = float(los[d])
+
+        self.a, self.b, self.pm, self.p, self.ke, self.me, self.ells = a, b, pm, p, ke, me, ells
+        self.s1 = 4 + 2 * len(ells)
+        be = backend.get()
+        self.kt = torch.from_numpy(ke).to(be.device)
+        self.mt = torch.from_numpy(me).to(be.device) if me is not None else None
+
+    def sums(self, a, b):
+        """the raw sums of pmx_power_project for the fields a and b (None: a) of this plan's layout, summed over the
+        ranks: a host vector"""
+        be = backend.get()
+        p = self.p
+        acc = torch.zeros(p.nk * self.s1 + p.nk * p.nmu * 5, dtype=torch.float64, device=be.device)
+        try:
+            be.power_project(p, a.value, b.value if b is not None else None, a.start, self.pm.Nmesh, self.pm.BoxSize,
+                             self.kt, self.mt, acc)
+        except backend.PmxError as e:
+            if e.code == _abi.PMX_EUNSUPPORTED:
+                raise ValueError(str(e))
+            raise
+        # one sum over the ranks of the raw sums, then the division
+        if self.pm.comm.size > 1:
+            acc = self.pm.comm.allreduce(acc)
+        return acc.cpu().numpy()
+
+    def result(self, acc):
+        return PowerResult(self.ke, self.me, acc, self.ells)
+
+
+def _same_layout(a, b):
+    if type(b) is not type(a) or tuple(b.start) != tuple(a.start) or tuple(b.value.shape) != tuple(a.value.shape) \
+            or b.value.dtype != a.value.dtype:
+        raise ValueError('the two fields must have the same layout and dtype (%s %s vs %s %s)'
+                         % (type(a).__name__, a.value.dtype, type(b).__name__, b.value.dtype))
+
+
 def power_spectrum(field, kedges, other=None, muedges=None, los=None, poles=(), deconv_pow=0):
     """The binned auto (other None) or cross power spectrum of `field` (and `other`): see the module docstring.
 
@@ -82,72 +173,133 @@ def power_spectrum(field, kedges, other=None, muedges=None, los=None, poles=(), 
     poles : multipole orders, each in 0..PMX_POWER_MAX_ELL, at most PMX_POWER_MAX_POLES of them.
     deconv_pow : divide v by prod_d sinc(w_d / 2)^deconv_pow (window compensation).
     """
-    a = _complex(field)
-    pm = a.pm
-    ndim = len(pm.Nmesh)
-    if ndim > _abi.PMX_MAXDIM:
-        raise NotImplementedError('power spectra of meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
-    b = None
-    if other is not None:
-        b = _complex(other)
-        if b.pm is not pm and (tuple(b.pm.Nmesh) != tuple(pm.Nmesh) or tuple(b.pm.BoxSize) != tuple(pm.BoxSize)
-                               or b.pm.comm is not pm.comm):
-            raise ValueError('the two fields belong to different meshes')
-        if type(b) is not type(a) or tuple(b.start) != tuple(a.start) or tuple(b.value.shape) != tuple(a.value.shape) \
-                or b.value.dtype != a.value.dtype:
-            raise ValueError('the two fields must have the same layout and dtype (%s %s vs %s %s)'
-                             % (type(a).__name__, a.value.dtype, type(b).__name__, b.value.dtype))
-    if a.value.dtype not in (torch.complex64, torch.complex128):
-        raise ValueError('power_spectrum measures complex64 or complex128 fields')
+    plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow)
+    return plan.result(plan.sums(plan.a, plan.b))
 
-    ke = _edges('kedges', kedges)
-    if len(ke) - 1 > _abi.PMX_POWER_MAX_KBINS:
-        raise ValueError('%d k bins: more than PMX_POWER_MAX_KBINS = %d' % (len(ke) - 1, _abi.PMX_POWER_MAX_KBINS))
-    me = None
-    if muedges is not None:
-        me = _edges('muedges', muedges, -1.0, 1.0)
-        if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
-            raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d' % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
-    ells = [int(ell) for ell in poles]
-    if len(ells) > _abi.PMX_POWER_MAX_POLES:
-        raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
-    if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
-        raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
-    if int(deconv_pow) != deconv_pow or deconv_pow < 0:
-        raise ValueError('deconv_pow must be a non-negative integer')
-    if los is None:
-        los = numpy.zeros(ndim)
-        los[-1] = 1.0
-    los = numpy.array(los, dtype='f8').reshape(-1)
-    norm = numpy.sqrt((los ** 2).sum())
-    if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
-        raise ValueError('los must be a nonzero vector of %d components' % ndim)
-    los = los / norm
 
-    p = _abi.Power()
-    p.nk = len(ke) - 1
-    p.nmu = 0 if me is None else len(me) - 1
-    p.npoles = len(ells)
-    for i, ell in enumerate(ells):
-        p.poles[i] = ell
-    p.hermitian = int(bool(a.compressed))
-    p.deconv_pow = int(deconv_pow)
-    p.volume = float(numpy.prod(pm.BoxSize))
-    for d in range(ndim):
-        p.los[d] = float(los[d])
+# ---- gradients -----------------------------------------------------------------------------------------------------
+
+def _complex_only(field):
+    from .pm import RealField, BaseComplexField
+    if isinstance(field, RealField):
+        raise TypeError('the gradients of power_spectrum take ComplexField objects: transform the RealField with r2c '
+                        'and back-propagate through it with r2c_vjp')
+    if not isinstance(field, BaseComplexField):
+        raise TypeError('power_spectrum measures RealField or ComplexField objects, not %s' % type(field).__name__)
+    return field
+
+
+def _cotangent(name, v, shape):
+    """a cotangent as a complex array of `shape` (None: zeros)"""
+    if v is None:
+        return numpy.zeros(shape, dtype='c16')
+    v = numpy.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+    if v.shape != tuple(shape):
+        raise ValueError('%s must have the shape %s of its spectrum, not %s' % (name, tuple(shape), v.shape))
+    return v.astype('c16')
+
+
+def power_spectrum_vjp(field, kedges, v_power=None, v_poles=None, v_power2d=None, other=None, muedges=None, los=None,
+                       poles=(), deconv_pow=0, result=None):
+    """The gradient of L = Re sum conj(v) P, summed over ``power``, every ``poles[ell]`` and ``power2d`` of
+    ``power_spectrum(field, kedges, other, muedges, los, poles, deconv_pow)``, with respect to the field(s): one kernel
+    (csrc/pmx_power_grad.hip, include/pmesh_amd.h: pmx_power_vjp), one read of each field and one write of each
+    gradient.
+
+    field, other : ComplexField objects as for power_spectrum (a RealField raises TypeError: go through r2c_vjp).
+    v_power : Nk real or complex values, v_poles : dict ell -> Nk values (keys among `poles`), v_power2d : (Nk, Nmu)
+        values (needs muedges); None counts as zero, and empty bins (NaN in the forward) contribute nothing.  ``k``,
+        ``mu2d`` and the counts are piecewise constant and have no gradient.
+    result : the PowerResult of the same arguments, for its counts; without it they come from one forward call.
+
+    Returns grad_field (other None) or (grad_field, grad_other): fields of the inputs' type in the form of lpt_vjp
+    and of RealField.c2r_vjp before decompress_vjp: ``Re(u.cdot(grad))`` is the derivative of L along u.
+    """
+    plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex_only)
+    p, nk, nmu, ells = plan.p, plan.p.nk, plan.p.nmu, plan.ells
+    if v_power2d is not None and plan.me is None:
+        raise ValueError('v_power2d needs muedges')
+    v_poles = dict(v_poles) if v_poles else {}
+    unknown = [ell for ell in v_poles if ell not in ells]
+    if unknown:
+        raise ValueError('v_poles has orders %s that are not among poles %s' % (unknown, ells))
+    v1 = _cotangent('v_power', v_power, (nk,))
+    vp = [_cotangent('v_poles[%d]' % ell, v_poles.get(ell), (nk,)) for ell in ells]
+    v2 = _cotangent('v_power2d', v_power2d, (nk, nmu)) if nmu else None
+
+    if result is None:
+        result = plan.result(plan.sums(plan.a, plan.b))
+    elif tuple(result.modes.shape) != (nk,) or (nmu > 0) != (result.modes2d is not None) or \
+            (nmu and tuple(result.modes2d.shape) != (nk, nmu)):
+        raise ValueError('result is not the PowerResult of these arguments')
+
+    # the coefficient table: acc's layout without the count, |k| and mu columns
+    sc = 2 + 2 * len(ells)
+    coef = numpy.zeros(nk * sc + nk * nmu * 2)
+    c1 = coef[:nk * sc].reshape(nk, sc)
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        inv = numpy.where(result.modes > 0, 1.0 / result.modes, 0.0)
+        cols = [v1 * inv] + [(2 * ell + 1) * v * inv for ell, v in zip(ells, vp)]
+        for i, c in enumerate(cols):
+            c1[:, 2 * i], c1[:, 2 * i + 1] = c.real, c.imag
+        if nmu:
+            inv2 = numpy.where(result.modes2d > 0, 1.0 / result.modes2d, 0.0)
+            c2 = coef[nk * sc:].reshape(nk, nmu, 2)
+            c2[..., 0], c2[..., 1] = (v2 * inv2).real, (v2 * inv2).imag
 
     be = backend.get()
-    s1 = 4 + 2 * len(ells)
-    acc = torch.zeros(p.nk * s1 + p.nk * p.nmu * 5, dtype=torch.float64, device=be.device)
-    kt = torch.from_numpy(ke).to(be.device)
-    mt = torch.from_numpy(me).to(be.device) if me is not None else None
+    a, b, pm = plan.a, plan.b, plan.pm
+    # (the kernel writes every mode of the block: only the GPU backend hands out raw memory)
+    from .pm import _blank
+
+    def new(f):
+        return _blank(type(f), pm) if be.name == 'hip' and f.value.numel() else pm.create(type=type(f))
+    ga = new(a)
+    gb = new(b) if b is not None else None
     try:
-        be.power_project(p, a.value, b.value if b is not None else None, a.start, pm.Nmesh, pm.BoxSize, kt, mt, acc)
+        be.power_vjp(p, a.value, b.value if b is not None else None, ga.value, gb.value if gb is not None else None,
+                     a.start, pm.Nmesh, pm.BoxSize, plan.kt, plan.mt, torch.from_numpy(coef).to(be.device))
     except backend.PmxError as e:
         if e.code == _abi.PMX_EUNSUPPORTED:
             raise ValueError(str(e))
         raise
-    # one sum over the ranks of the raw sums, then the division
-    if pm.comm.size > 1:
-        acc = pm.comm.allreduce(acc)
-    return PowerResult(ke, me, acc.cpu().numpy(), ells)
+    return ga if b is None else (ga, gb)
+
+
+def power_spectrum_jvp(field, kedges, v_field=None, v_other=None, other=None, muedges=None, los=None, poles=(),
+                       deconv_pow=0):
+    """The tangent of power_spectrum along v_field (and v_other): a PowerResult whose ``power``, ``poles`` and
+    ``power2d`` are tangents and whose ``k``, ``modes``, ``k2d``, ``mu2d`` and ``modes2d`` are the forward's.
+
+    The raw sums are bilinear in (a, b), so the tangent of every power-like column is acc(da, b) + acc(a, db): two
+    cross calls of the forward kernel, divided by the forward's counts (for the auto spectrum b = a and db = da).
+    v_field, v_other : ComplexField objects of the fields' layout; None counts as zero."""
+    plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex_only)
+    a, b = plan.a, plan.b
+    if v_other is not None and b is None:
+        raise ValueError('v_other needs other')
+    terms = []
+    for v, partner, first in ((v_field, b if b is not None else a, True), (v_other, a, False)):
+        if v is None:
+            continue
+        v = _complex_only(v)
+        _same_layout(a, v)
+        terms.append((v, partner) if first else (partner, v))
+    if b is None and terms:
+        terms.append((a, terms[0][0]))                       # acc(a, da): the second half of the auto tangent
+    if not terms:
+        terms = [(a, b)]                                     # for the counts alone
+    accs = [plan.sums(x, y) for x, y in terms]
+    acc = sum(accs)
+    # counts, |k| and mu sums are the same in every term: the forward's
+    nk, s1, nmu = plan.p.nk, plan.s1, plan.p.nmu
+    t1 = acc[:nk * s1].reshape(nk, s1)
+    t1[:, :2] /= len(accs)
+    if nmu:
+        t2 = acc[nk * s1:].reshape(nk, nmu, 5)
+        t2[..., :3] /= len(accs)
+    if v_field is None and v_other is None:
+        t1[:, 2:] = 0
+        if nmu:
+            t2[..., 3:] = 0
+    return plan.result(acc)

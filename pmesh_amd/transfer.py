@@ -139,6 +139,9 @@ class Tabulated(Transfer):
     every Transfer it is also a ``func(k, v)`` callable evaluated with array operators on the host or device.
 
         delta_k = pm.generate_whitenoise(seed, unitary=True).apply(Tabulated(k, (P / V) ** 0.5, loglog=True))
+
+    ``apply_vjp`` and ``apply_jvp`` are its gradients with respect to the field and to the values t (band powers,
+    transfer-function nodes); the abscissae k have none.
     """
 
     def __init__(self, k, t, loglog=False, amplitude=1.0, left=0.0, right=0.0):
@@ -190,6 +193,81 @@ class Tabulated(Transfer):
             return
         x, y, s = self._table(be.device)
         be.apply_ktable(s, v, outv, field.start, field.Nmesh, field.BoxSize)
+
+    # ---- gradients with respect to the field and the table values --------------------------------------------------
+
+    def _check(self, name, f, like=None):
+        from .pm import BaseComplexField
+        if not isinstance(f, BaseComplexField):
+            raise TypeError('%s must be a ComplexField, not %s' % (name, type(f).__name__))
+        if f.value.dim() > _abi.PMX_MAXDIM:
+            raise NotImplementedError('tabulated transfers on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
+        if like is not None and (type(f) is not type(like) or tuple(f.value.shape) != tuple(like.value.shape)
+                                 or tuple(f.start) != tuple(like.start) or f.value.dtype != like.value.dtype):
+            raise ValueError('%s must have the layout and dtype of the field' % name)
+        return f
+
+    def apply_vjp(self, field, v, out_t=True):
+        """The gradients of ``field.apply(self)`` for the cotangent v (a ComplexField of field's layout):
+        (grad_field, grad_t).  grad_field = v.apply(self) (T is real: its own adjoint).  grad_t (out_t) is a numpy
+        array of len(t), summed over pm.comm: the derivative of Re(v.cdot(field.apply(self))) with respect to t,
+
+            grad_t[i] = amplitude * sum_m w_m Re(conj(v_m) field_m) dinterp(|k_m|) / dt_i
+
+        by one reduction kernel (csrc/pmx_ktable_grad.hip, include/pmesh_amd.h: pmx_ktable_vjp).  Between two entries
+        a linear table weighs them 1 - f and f; a log-log table the same times interp(|k|) / t_i; outside the table
+        `left` and `right` are constants and the weight is 0."""
+        self._check('field', field)
+        self._check('v', v, field)
+        grad_field = v.apply(self)
+        if not out_t:
+            return grad_field, None
+        be = backend.get()
+        n = len(self.t)
+        g = torch.zeros(n, dtype=torch.float64, device=be.device)
+        if field.value.numel():
+            x, y, s = self._table(be.device)
+            be.ktable_vjp(s, field.compressed, field.value, v.value, field.start, field.Nmesh, field.BoxSize, g)
+        comm = field.pm.comm
+        if comm.size > 1:
+            g = comm.allreduce(g)
+        g = g.cpu().numpy() * self.amplitude
+        if self.loglog:
+            g = g / self.t
+        return grad_field, g
+
+    def apply_jvp(self, field, v_field=None, v_t=None):
+        """The tangent of ``field.apply(self)`` along v_field (a ComplexField of field's layout) and v_t (len(t)
+        values): a ComplexField.  The field part is v_field.apply(self); the table part of a linear table is the
+        table of v_t applied to the field, that of a log-log table T(|k|) times the interpolation in ln k of v_t / t
+        (the kernel pmx_apply_ktable_jvp)."""
+        self._check('field', field)
+        out = None
+        if v_field is not None:
+            out = self._check('v_field', v_field, field).apply(self)
+        if v_t is not None:
+            v_t = numpy.array(v_t, dtype='f8')
+            if v_t.shape != self.t.shape or not numpy.isfinite(v_t).all():
+                raise ValueError('v_t must hold %d finite values' % len(self.t))
+            if not self.loglog:
+                part = field.apply(Tabulated(self.k, v_t, amplitude=self.amplitude, left=0.0, right=0.0))
+            else:
+                be = backend.get()
+                from .pm import _blank
+                hip = be.name == 'hip' and field.value.numel()
+                part = _blank(type(field), field.pm) if hip else field.pm.create(type=type(field))
+                if field.value.numel():
+                    x, y, s = self._table(be.device)
+                    dy = torch.from_numpy(v_t / self.t).to(be.device)
+                    be.apply_ktable_jvp(s, dy, field.value, part.value, field.start, field.Nmesh, field.BoxSize)
+            if out is None:
+                out = part
+            else:
+                out.value[...] += part.value
+        if out is None:
+            out = field.pm.create(type=type(field))
+            out.value[...] = 0
+        return out
 
     def interp(self, kmag):
         """interp(|k|) of the class docstring on a numpy array"""
