@@ -778,6 +778,10 @@ int pmo_apply_transfer(const pmx_transfer *t, int32_t ndim, int32_t elsize, cons
                        const double *boxsize, void *stream)
 {
     (void)stream;
+    /* the argument checks of pmx_apply_transfer (csrc/pmx_transfer.hip) */
+    if (!t || ndim < 1 || ndim > 3) return PMX_EINVAL;
+    if (elsize != 4 && elsize != 8) return PMX_EINVAL;
+    if (t->grad_dir >= ndim) return PMX_EINVAL;
     int64_t n[3] = {1, 1, 1}, is[3] = {0, 0, 0}, os[3] = {0, 0, 0}, st[3] = {0, 0, 0};
     int64_t nm[3] = {1, 1, 1};
     double L[3] = {1, 1, 1};

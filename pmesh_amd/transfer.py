@@ -94,9 +94,30 @@ class Transfer(object):
                 _abi.i64arr(field.start, 3), _abi.i64arr(field.Nmesh, 3),
                 _abi.f64arr(field.BoxSize, 3), be.stream())
 
+    @staticmethod
+    def _double_wavenumbers(k, v):
+        """The kernel evaluates T in double from the mode's index whatever the precision of the mesh, and so does this
+        form: the wavenumbers Field.apply hands out on an f4 mesh are rounded to float32 (as the reference casts
+        them), so they are recomputed from the mode numbers the slab carries (v.i, v.BoxSize, v.Nmesh; the roundings
+        of pm._block_coords in float64), or widened where it carries none.  float64 wavenumbers pass through."""
+        if all(str(ki.dtype).endswith('float64') for ki in k):
+            return k
+
+        def f8(a):
+            return a.to(torch.float64) if isinstance(a, torch.Tensor) else a.astype('f8')
+        i = getattr(v, 'i', None)
+        if i is None or not hasattr(v, 'BoxSize') or not hasattr(v, 'Nmesh'):
+            return [f8(ki) for ki in k]
+        out = []
+        for ii, L, N in zip(i, v.BoxSize, v.Nmesh):
+            N = int(N)
+            out.append(f8(ii - N * (ii >= N // 2)) * (2 * numpy.pi / N) * N / float(L))
+        return out
+
     def __call__(self, k, v):
         """ the same transfer as a reference-style filter func(k, v), kind='wavenumber' """
         xp_sin, xp_exp = (torch.sin, torch.exp) if isinstance(v, torch.Tensor) else (numpy.sin, numpy.exp)
+        k = self._double_wavenumbers(k, v)
         k2 = sum(ki ** 2 for ki in k)
         r = self.amplitude
         if self.laplace_pow:

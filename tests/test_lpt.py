@@ -327,8 +327,10 @@ def test_ranks_equal_one(lbe, size, np_):
 def _block(shape, dtype, form, rng, complex_=True):
     """a block of the given logical shape as a tensor on the device: contiguous ('C'), axes 0 / 1 swapped in memory
     ('T', the transposed layout), padded along the last axis ('pad') or every other element of a larger array
-    ('strided')"""
+    ('strided'); a 1-d block has no axes to swap, its 'T' is 'C'"""
     dev = backend.get().device
+    if form == 'T' and len(shape) == 1:
+        form = 'C'
     if form == 'T':
         big = (shape[1], shape[0]) + tuple(shape[2:])
     elif form == 'pad':
@@ -349,10 +351,35 @@ def _block(shape, dtype, form, rng, complex_=True):
 
 
 FORMS = ['C', 'T', 'pad', 'strided']
+# The streaming kernels launch min(rows, WRAP) workgroups along the slowest memory axis and walk it in steps of that
+# many: in a block with more rows a workgroup makes a second trip.  Tall blocks (a 1-d mesh of 2^17 points, a tall 2-d
+# block) reach it; under form 'T' the long axis is the slow one in memory only for the second of them.
+WRAP = 65535
+TALL = [([65541, 3], [1000, 0], [131072, 4]),
+        ([3, 65541], [0, 1000], [4, 131072]),
+        ([65541, 2, 3], [1000, 0, 0], [131072, 2, 4])]
+TALL_1D = [([65541], [1000], [131072])]                   # for the kernels that take ndim == 1
 GEOMS = [([16, 16, 9], [0, 0, 0], [16, 16, 16]),          # an r2c half spectrum
          ([45, 15, 45], [0, 0, 0], [45, 45, 45]),         # odd, a block of a c2c spectrum
          ([12, 48, 25], [36, 0, 0], [48, 48, 48]),        # 3 * 2^k, a slab starting at 36
-         ([24, 17], [0, 0], [24, 32])]                    # 2-d
+         ([24, 17], [0, 0], [24, 32])] + TALL + TALL_1D   # 2-d; then more rows than WRAP
+
+
+def _nan_block(shape, dtype, form, rng, complex_=True):
+    """a _block filled with NaN: an output in which an element the kernel never writes cannot pass"""
+    t = _block(shape, dtype, form, rng, complex_)
+    return t.fill_(complex(float('nan'), float('nan')) if complex_ else float('nan'))
+
+
+def close_rows(got, want, tol):
+    """close on the whole block, then on the rows from WRAP on of an axis that long, on their own scale"""
+    close(got, want, tol)
+    got, want = numpy.asarray(got), numpy.asarray(want)
+    for d, n in enumerate(want.shape):
+        if n > WRAP:
+            sel = (slice(None),) * d + (slice(WRAP, None),)
+            assert numpy.isfinite(got[sel]).all()
+            close(got[sel], want[sel], tol)
 
 
 @pytest.mark.gpu
@@ -369,12 +396,12 @@ def test_ktable_kernel(hipbe, form, cdt, tol, loglog):
         v = _block(shape, cdt, form, rng)
         kk = block_k(start, shape, nmesh, box)
         want = scaled(ref_factor(k, t, numpy.sqrt(k_squared(kk)), loglog, 1.5, 0.5, 2.0), cpu(v))
-        out = _block(shape, cdt, 'pad' if form != 'pad' else 'C', rng)
+        out = _nan_block(shape, cdt, 'pad' if form != 'pad' else 'C', rng)
         x, y, s = tab._table(hipbe.device)
         hipbe.apply_ktable(s, v, out, start, nmesh, box)
-        close(cpu(out), want, tol)
+        close_rows(cpu(out), want, tol)
         hipbe.apply_ktable(s, v, v, start, nmesh, box)           # in place
-        close(cpu(v), want, tol)
+        close_rows(cpu(v), want, tol)
 
 
 @pytest.mark.gpu
@@ -390,13 +417,17 @@ def test_hessian_kernel(hipbe, form, cdt, tol):
         for group in (pairs[:1], pairs[:2], pairs[-3:]):
             v = _block(shape, cdt, form, rng)
             want = [scaled(hessian_factor(kk, i, j), cpu(v)) for i, j in group]
-            outs = [_block(shape, cdt, f, rng) for f in ('C', 'pad', 'T')[:len(group)]]
+            outs = [_nan_block(shape, cdt, f, rng) for f in ('C', 'pad', 'T')[:len(group)]]
             hipbe.lpt_hessian(v, group, outs, start, nmesh, box)
             for o, w in zip(outs, want):
-                close(cpu(o), w, tol)
+                close_rows(cpu(o), w, tol)
             # in place: the last output is the input itself
             hipbe.lpt_hessian(v, group, outs[:-1] + [v], start, nmesh, box)
-            close(cpu(v), want[-1], tol)
+            close_rows(cpu(v), want[-1], tol)
+
+
+# the real blocks of the source kernel and its gradients (ndim 2 or 3), the tall ones among them
+SOURCE_SHAPES = [[16, 16, 16], [45, 15, 45], [12, 48, 50], [24, 34]] + [g[0] for g in TALL]
 
 
 @pytest.mark.gpu
@@ -404,16 +435,16 @@ def test_hessian_kernel(hipbe, form, cdt, tol):
 @pytest.mark.parametrize('rdt,tol', [('f8', 1e-12), ('f4', 1e-5)])
 def test_source_kernel(hipbe, form, rdt, tol):
     rng = numpy.random.RandomState(8)
-    for shape in ([16, 16, 16], [45, 15, 45], [12, 48, 50], [24, 34]):
+    for shape in SOURCE_SHAPES:
         nd = len(shape)
         ins = [_block(shape, rdt, f, rng, complex_=False) for f in (FORMS * 2)[:3 if nd == 2 else 6]]
         ins[0] = _block(shape, rdt, form, rng, complex_=False)
         want = source([cpu(a) for a in ins], 0.375)
-        out = _block(shape, rdt, 'strided' if form != 'strided' else 'C', rng, complex_=False)
+        out = _nan_block(shape, rdt, 'strided' if form != 'strided' else 'C', rng, complex_=False)
         hipbe.lpt2_source(ins, out, 0.375)
-        close(cpu(out), want, tol)
+        close_rows(cpu(out), want, tol)
         hipbe.lpt2_source(ins, ins[0], 0.375)                     # out aliases the first input
-        close(cpu(ins[0]), want, tol)
+        close_rows(cpu(ins[0]), want, tol)
 
 
 @pytest.mark.gpu

@@ -16,7 +16,8 @@ import torch
 from pmesh_amd import _abi, backend
 from pmesh_amd.pm import ParticleMesh, TransposedComplexField, UntransposedComplexField
 from pmesh_amd.transfer import Tabulated
-from tests.test_lpt import LptOracleBackend, _host_doubles, block_k, k_squared, table
+from tests.test_lpt import (FORMS, TALL, TALL_1D, WRAP, LptOracleBackend, _block, _host_doubles, _nan_block, block_k,
+                            k_squared, table)
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------
@@ -362,6 +363,70 @@ def test_kernels_against_restatement(hipbe, kind, dtype, loglog):
                 assert (jerr <= tol).all(), (n, uniform, jerr.max() / jscale, jown / jscale)
             print('ktable_jvp %s %s loglog=%d n=%d uniform=%d: restatement vs longdouble %.2e of scale'
                   % (kind, dtype, loglog, n, uniform, jown / jscale))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('form', FORMS)
+@pytest.mark.parametrize('cdt', ['c16', 'c8'])
+@pytest.mark.parametrize('loglog', [False, True])
+def test_kernels_on_tall_blocks(hipbe, form, cdt, loglog):
+    """pmx_ktable_vjp and pmx_apply_ktable_jvp called on blocks whose slowest axis has more rows than the launch grid
+    (test_lpt.WRAP), in every memory form: against the restatement, the tangent also row by row into an output that
+    starts as NaN, and the sums of the rows from WRAP on alone against the whole block's less its first WRAP rows'.
+    Tables of 40 entries: a rounding of |k| in the last place moves the fraction f by 40 units in the last place, so
+    sums and tangents are held to the 1e-12 of their scale of test_kernels_against_restatement without its allowance
+    for the restatement's own rounding (a complex64 tangent also to 2^-24 per component: a double rounded once)."""
+    rng = numpy.random.RandomState(22)
+    n = 40
+    for gi, (shape, start, nmesh) in enumerate(TALL + TALL_1D):
+        nd = len(shape)
+        box = [100., 80., 120.][:nd]
+        long = int(numpy.argmax(shape))
+        k = block_k(start, shape, nmesh, box)
+        kmag = numpy.broadcast_to(numpy.sqrt(k_squared(k)), tuple(shape))
+        lo, hi = 1.5 * kmag[kmag > 0].min(), 0.995 * kmag.max()
+        if gi % 2:                                              # uniform (the guessed search) and irregular tables
+            kt = numpy.geomspace(lo, hi, n) if loglog else numpy.linspace(lo, hi, n)
+        else:
+            steps = numpy.arange(n, dtype='f8')
+            steps[1:-1] += rng.uniform(-0.4, 0.4, n - 2)
+            kt = lo + (hi - lo) * steps / (n - 1)
+        tab = Tabulated(kt, (1.0 + 0.5 * numpy.sin(7 * kt / hi)) * (kt / lo) ** -0.7, loglog=loglog, amplitude=1.3,
+                        left=0.2, right=0.1)
+        past = numpy.take(kmag, numpy.arange(WRAP, shape[long]), axis=long)
+        assert ((past >= kt[0]) & (past <= kt[-1])).all() and (kmag < kt[0]).any() and (kmag > kt[-1]).any()
+        hermitian = gi % 2 == 0
+        a = _block(shape, cdt, form, rng)
+        V = _block(shape, cdt, 'pad' if form != 'pad' else 'C', rng)
+        x, y, s = tab._table(hipbe.device)
+
+        def sums(rows, first):
+            sel = (slice(None),) * long + (rows,)
+            st = list(start)
+            st[long] += first
+            g = torch.zeros(n, dtype=torch.float64, device=hipbe.device)
+            hipbe.ktable_vjp(s, hermitian, a[sel], V[sel], st, nmesh, box, g)
+            return cpu(g)
+        whole, head, tail = sums(slice(None), 0), sums(slice(0, WRAP), 0), sums(slice(WRAP, None), WRAP)
+        want = ktable_vjp_ref(tab._x, tab._y, loglog, float(kt[0]), float(kt[-1]), cpu(a), cpu(V), k,
+                              _last_index(start, shape), int(nmesh[-1]), hermitian)
+        scale = numpy.abs(want).max()
+        assert numpy.abs(whole - want).max() <= 1e-12 * scale, (shape, numpy.abs(whole - want).max() / scale)
+        assert numpy.abs(tail).max() > 1e-6 * scale
+        assert numpy.abs((whole - head) - tail).max() <= 1e-12 * scale, (shape, whole - head, tail)
+        # the tangent, out of place and in place
+        dy = rng.normal(size=n)
+        dyd = torch.from_numpy(dy).to(hipbe.device)
+        jvp = ktable_jvp_ref(tab._x, tab._y, dy, loglog, tab.amplitude, float(kt[0]), float(kt[-1]), cpu(a), k)
+        jscale = numpy.abs(jvp).max()
+        out = _nan_block(shape, cdt, 'strided' if form != 'strided' else 'C', rng)
+        hipbe.apply_ktable_jvp(s, dyd, a, out, start, nmesh, box)
+        hipbe.apply_ktable_jvp(s, dyd, a, a, start, nmesh, box)
+        for got in (cpu(out).astype('c16'), cpu(a).astype('c16')):
+            for got_c, want_c in ((got.real, jvp.real), (got.imag, jvp.imag)):
+                tol = 1e-12 * jscale + (2.0 ** -24 * numpy.abs(want_c) if cdt == 'c8' else 0.0)
+                assert (numpy.abs(got_c - want_c) <= tol).all(), (shape, numpy.abs(got_c - want_c).max() / jscale)
+            assert numpy.isfinite(numpy.take(got, numpy.arange(WRAP, shape[long]), axis=long)).all()
 
 
 # ---- ranks equal one -----------------------------------------------------------------------------------------------

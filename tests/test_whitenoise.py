@@ -83,6 +83,48 @@ def test_generate_equals_golden(be, golden, master, monkeypatch):
         assert_array_equal(got.imag == 0, value.imag == 0)
 
 
+# past the golden vectors (32^3: 17 modes per column, 3 refills of a RANLUX stream, 512 columns): non-cubic and
+# 3 * 2^k meshes, blocks cut along every axis, up to 1026 draws per stream (86 refills through the kernel's register
+# ring) and the two passes of a full spectrum; (nmesh, start, shape, dtype, unitary, seed), one seed with bit 31 set
+LARGE = [((64, 48, 128), (0, 0, 0), (64, 48, 65), 'c16', False, 20240917),      # non-cubic, 24 workgroups, 11 refills
+         ((64, 48, 128), (16, 8, 0), (24, 20, 65), 'c8', False, 7),             # a pencil block
+         ((64, 48, 128), (0, 0, 33), (64, 48, 32), 'c16', True, 0x9E3779B9),    # cut along the last axis, Nyquist inside
+         ((96, 96, 96), (0, 0, 0), (96, 96, 49), 'c16', True, 314159),          # 3 * 2^k ring order, 72 workgroups
+         ((16, 16, 1024), (3, 0, 0), (9, 16, 513), 'c16', False, 99),           # 1026 draws per stream, 86 refills
+         ((32, 32, 64), (0, 0, 0), (32, 32, 64), 'c8', False, 5463)]            # full c2c spectrum, both passes
+_large_want = {}
+
+
+def large_want(oracle, n):
+    """the oracle's block of LARGE[n], computed once and shared; where the reference's own compiled C is at hand the
+    oracle is first held to it bit for bit"""
+    if n not in _large_want:
+        nmesh, start, shape, dtype, unitary, seed = LARGE[n]
+        want = oracle.whitenoise(shape, start, nmesh, seed, unitary, dtype)
+        if oracle.have_whitenoise_ref():
+            assert_array_equal(want, oracle.whitenoise_ref(shape, start, nmesh, seed, unitary, dtype))
+        want.setflags(write=False)
+        _large_want[n] = want
+    return _large_want[n]
+
+
+@pytest.mark.parametrize('n,master', [(0, 'host'), (0, 'device')] + [(n, 'default') for n in range(1, len(LARGE))])
+def test_generate_equals_oracle_at_scale(be, oracle, n, master, monkeypatch):
+    if master == 'device' and be.name != 'hip':
+        pytest.skip('the device form of the master stream needs the HIP backend')
+    if master != 'default':
+        from pmesh_amd import whitenoise as wn
+        monkeypatch.setattr(wn, 'MASTER_ON_DEVICE', master == 'device')
+    nmesh, start, shape, dtype, unitary, seed = LARGE[n]
+    want = large_want(oracle, n)
+    t = torch.zeros(shape, dtype=torch.complex128 if dtype == 'c16' else torch.complex64, device=be.device)
+    generate(t, start, nmesh, seed, unitary)
+    got = t.cpu().numpy()
+    ulp_close(got, want)
+    assert_array_equal(got == 0, want == 0)
+    assert_array_equal(got.imag == 0, want.imag == 0)
+
+
 def test_generate_strided_and_host_arrays(be, oracle):
     nmesh, start, shape = (16, 16, 16), (2, 0, 1), (9, 16, 7)
     want = oracle.whitenoise(shape, start, nmesh, 99)
