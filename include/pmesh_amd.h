@@ -549,6 +549,44 @@ int pmx_power_vjp(const pmx_power *p, int32_t ndim, int32_t elsize, const void *
                   const double *boxsize, const double *kedges, const double *muedges, const double *coef,
                   void *stream);
 
+/* ---- binned bispectrum (what bskit-style estimators compose from ComplexField.apply, c2r and products of real
+ * fields: pmesh_amd.bispectrum.bispectrum) --------------------------------------------------------------------------
+ * Shells are the k bins of pmx_power_project: shell(m) = j when kedges[j] <= |k_m| < kedges[j + 1], with k_d and |k|
+ * computed as stated there, so a mode is in the same shell in both. */
+
+#define PMX_BISPEC_MAX_SHELLS 64           /* shells per call */
+#define PMX_BISPEC_MAX_TRIANGLES 45760     /* triples i <= j <= l of 64 shells */
+
+/* Splits the local complex block a into nb shell spectra in one read, replacing one masked copy of the spectrum per
+ * shell (ComplexField.apply with a mask on |k|): for every stored mode m and every shell s
+ *   out[s][m] = a[m] / prod_d sinc(pi s_d / N_d)^deconv_pow   when shell(m) == s   (divided axis by axis, d = 0, 1, 2)
+ *               0                                             otherwise,
+ * and with unit != 0 the indicator: 1 in place of the (deconvolved) mode; a is then not read and may be NULL.  Every
+ * element of every output is written: the outputs may be raw memory.  Geometry as in pmx_power_project: logical
+ * shape[0..ndim) at global index start[], byte strides a_strides for a and out_strides (one set of ndim strides) for
+ * all outputs, ndim 1..3, elsize 4 (complex64) or 8 (complex128) per component, any axis order (transposed or
+ * untransposed, compressed or full spectra).  out is a host array of nb device pointers; kedges a DEVICE array of
+ * nb + 1 float64.  nb above PMX_BISPEC_MAX_SHELLS returns PMX_EUNSUPPORTED. */
+int pmx_bispec_shells(int32_t ndim, int32_t elsize, int32_t nb, int32_t deconv_pow, int32_t unit, const void *a,
+                      const int64_t *a_strides, void *const *out, const int64_t *out_strides, const int64_t *shape,
+                      const int64_t *start, const int64_t *nmesh, const double *boxsize, const double *kedges,
+                      void *stream);
+
+/* Adds, for each of ntri triples (i, j, l) = triangles[3 t .. 3 t + 3) (a DEVICE array of int32),
+ *   acc[t] += sum_x fields[i][x] * fields[j][x] * fields[l][x]        ((D_i D_j) D_l, products and sums in double)
+ * over the cells x of nb real blocks of one logical shape[0..ndim) and one set of byte strides (a padded last axis is
+ * a stride), elsize 4 or 8, replacing one (D_i * D_j * D_l).sum() over whole fields per triple: every block is read
+ * from device memory once per call, whatever ntri.  fields is a host array of nb device pointers; acc a DEVICE array
+ * of ntri float64 that the caller has zeroed (and, on several ranks, sums over the ranks).  work is a DEVICE array of
+ * work_doubles >= ntri float64 of any content: it holds one row of ntri partial sums per workgroup (at most 512 rows
+ * are used; fewer rows, fewer workgroups), which a second kernel adds into acc in fixed order — the result is the same
+ * bit for bit from run to run for the same shapes and work_doubles.  A triple that names a shell outside [0, nb) gives
+ * NaN.  Consecutive triples that share (i, j) reuse the pair product.  nb above PMX_BISPEC_MAX_SHELLS or ntri above
+ * PMX_BISPEC_MAX_TRIANGLES returns PMX_EUNSUPPORTED. */
+int pmx_bispec_reduce(int32_t ndim, int32_t elsize, int32_t nb, const void *const *fields, const int64_t *strides,
+                      const int64_t *shape, int32_t ntri, const int32_t *triangles, double *acc, double *work,
+                      int64_t work_doubles, void *stream);
+
 /* ---- initial conditions: tabulated transfers and second-order LPT (the reference's examples/nbody.py:245-282 builds
  * its linear field with a tabulated P(k) through Field.apply; nbody/genic.py:121-166 the 2LPT displacements) --------
  * Geometry as in pmx_apply_transfer: a local block of logical shape[0..ndim) at global index start[], byte strides

@@ -94,6 +94,9 @@ class Power(C.Structure):
     ]
 
 
+PMX_BISPEC_MAX_SHELLS = 64
+PMX_BISPEC_MAX_TRIANGLES = 45760
+
 PMX_KTABLE_MAX = 8192
 
 
@@ -188,6 +191,9 @@ DEVICE_ONLY = {
                                 _P(_f64), _vp, _vp, _vp, _vp]),
     'power_vjp': (C.c_int, [_P(Power), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _vp, _P(_i64), _vp, _P(_i64), _P(_i64),
                             _P(_i64), _P(_i64), _P(_f64), _vp, _vp, _vp, _vp]),
+    'bispec_shells': (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _P(_i64), _P(_vp), _P(_i64), _P(_i64), _P(_i64),
+                                _P(_i64), _P(_f64), _vp, _vp]),
+    'bispec_reduce': (C.c_int, [_i32, _i32, _i32, _P(_vp), _P(_i64), _P(_i64), _i32, _vp, _vp, _vp, _i64, _vp]),
     'apply_ktable': (C.c_int, [_P(KTable), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
                                _P(_f64), _vp]),
     'ktable_vjp': (C.c_int, [_P(KTable), _i32, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),

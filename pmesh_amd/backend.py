@@ -235,6 +235,44 @@ class HipBackend(object):
                   _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), kedges.data_ptr(),
                   muedges.data_ptr() if muedges is not None else None, coef.data_ptr(), self.stream())
 
+    # -- binned bispectrum ---------------------------------------------------
+    def bispec_shells(self, a, outs, start, nmesh, boxsize, kedges, deconv_pow=0, unit=False):
+        """outs[s] = the modes of the local complex block `a` in shell s (divided by the window; with unit: 1 there,
+        and `a` is not read), 0 elsewhere, for the len(outs) shells of the float64 device vector `kedges`; the outputs
+        share one shape, dtype and set of strides and may be raw memory (pmx_bispec_shells)"""
+        o = outs[0]
+        if o.numel() == 0:
+            return
+        es = o.element_size()
+        ptrs = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+        self.call('bispec_shells', o.dim(), es // 2, len(outs), int(deconv_pow), int(bool(unit)),
+                  None if unit else a.data_ptr(), None if unit else _abi.i64arr([s * es for s in a.stride()], 3), ptrs,
+                  _abi.i64arr([s * es for s in o.stride()], 3), _abi.i64arr(o.shape, 3), _abi.i64arr(start, 3),
+                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), kedges.data_ptr(), self.stream())
+
+    def bispec_reduce(self, fields, triangles, acc, work=None):
+        """acc[t] += sum over the cells of fields[i] * fields[j] * fields[l] for (i, j, l) = triangles[t]: real blocks
+        of one shape, dtype and set of strides, an int32 device array (ntri, 3), a float64 device vector; work: a
+        float64 device vector for the per-workgroup partial sums (None: allocated here) (pmx_bispec_reduce)"""
+        f = fields[0]
+        ntri = int(triangles.shape[0])
+        if f.numel() == 0 or ntri == 0:
+            return
+        es = f.element_size()
+        if work is None:
+            work = torch.empty(self.bispec_work(ntri, f.numel()), dtype=torch.float64, device=self.device)
+        ptrs = (C.c_void_p * len(fields))(*[t.data_ptr() for t in fields])
+        self.call('bispec_reduce', f.dim(), es, len(fields), ptrs, _abi.i64arr([s * es for s in f.stride()], 3),
+                  _abi.i64arr(f.shape, 3), ntri, triangles.data_ptr(), acc.data_ptr(), work.data_ptr(), work.numel(),
+                  self.stream())
+
+    @staticmethod
+    def bispec_work(ntri, ncells):
+        """doubles of work for bispec_reduce: a row per workgroup, up to 512 rows and 64 MB, no more rows than
+        chunks of 128 cells"""
+        rows = max(1, min(512, (1 << 23) // max(ntri, 1), (ncells + 127) // 128))
+        return rows * ntri
+
     # -- initial conditions: tabulated transfer, 2LPT ----------------------
     def apply_ktable(self, table, v, out, start, nmesh, boxsize):
         """out = T(|k|) v over the local complex block v (pmx_apply_ktable; `table` a _abi.KTable whose x / y are
