@@ -66,6 +66,17 @@ if _raw_stream is None:
         return torch.cuda.current_stream(index).cuda_stream
 
 
+def _byte_strides(t):
+    """the strides of tensor t in bytes, padded to three axes"""
+    es = t.element_size()
+    return _abi.i64arr([s * es for s in t.stride()], 3)
+
+
+def _mesh_args(start, nmesh, boxsize):
+    """start, Nmesh and BoxSize of a block as the three consecutive array arguments of the C ABI"""
+    return _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3)
+
+
 class HipBackend(object):
     """libpmesh_amd.so on cuda:<index> (ROCm)."""
     name = 'hip'
@@ -118,7 +129,7 @@ class HipBackend(object):
         (a_stride / n_stride: padded strides between successive a / lines n, 0 = dense)"""
         self.call('colfft', elsize, int(bool(inverse)), data.data_ptr(), A, N, B, float(scale),
                   C.byref(transfer) if transfer is not None else None, n1, n2,
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3),
+                  *_mesh_args(start, nmesh, boxsize),
                   int(a_stride), int(n_stride), self.stream())
 
     def colfft_configure(self, persistent):
@@ -134,7 +145,7 @@ class HipBackend(object):
         """forward column FFT x scale [x transfer] x inverse column FFT in one kernel, in place on (N, B)"""
         self.call('colfft_roundtrip', elsize, data.data_ptr(), N, B, float(scale),
                   C.byref(transfer) if transfer is not None else None, n1, n2,
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), int(n_stride), self.stream())
+                  *_mesh_args(start, nmesh, boxsize), int(n_stride), self.stream())
 
     def colfft_split(self, elsize, inverse, src, dst, A, N, B, nsplit, scale=1.0, plain_pitch=0):
         """column FFT fused with the slab pack (forward: plain -> split) / unpack (inverse);
@@ -155,7 +166,7 @@ class HipBackend(object):
         self.call('colfft_chunk', elsize, int(bool(inverse)), chunk.data_ptr(), full.data_ptr(), N, n1, cw,
                   pitch, coff, int(bool(to_full)), float(scale),
                   C.byref(transfer) if transfer is not None else None,
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+                  *_mesh_args(start, nmesh, boxsize), self.stream())
 
     def rowfft_supported(self, n, elsize):
         return self.lib.pmx_rowfft_supported(int(n), int(elsize)) == 0
@@ -185,7 +196,7 @@ class HipBackend(object):
         """colfft from `src` into `dst` (same layout)"""
         self.call('colfft_to', elsize, int(bool(inverse)), src.data_ptr(), dst.data_ptr(), A, N, B, float(scale),
                   C.byref(transfer) if transfer is not None else None, n1, n2,
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3),
+                  *_mesh_args(start, nmesh, boxsize),
                   int(a_stride), int(n_stride), self.stream())
 
     # -- slab transposes --------------------------------------------------
@@ -211,10 +222,10 @@ class HipBackend(object):
             return
         es = a.element_size()
         nd = a.dim()
-        self.call('power_project', C.byref(params), nd, es // 2, a.data_ptr(), _abi.i64arr([s * es for s in a.stride()], 3),
+        self.call('power_project', C.byref(params), nd, es // 2, a.data_ptr(), _byte_strides(a),
                   b.data_ptr() if b is not None else None,
-                  _abi.i64arr([s * es for s in b.stride()], 3) if b is not None else None,
-                  _abi.i64arr(a.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3),
+                  _byte_strides(b) if b is not None else None,
+                  _abi.i64arr(a.shape, 3), *_mesh_args(start, nmesh, boxsize),
                   kedges.data_ptr(), muedges.data_ptr() if muedges is not None else None, acc.data_ptr(),
                   self.stream())
 
@@ -226,13 +237,13 @@ class HipBackend(object):
         es = a.element_size()
 
         def strides(t):
-            return _abi.i64arr([s * es for s in t.stride()], 3) if t is not None else None
+            return _byte_strides(t) if t is not None else None
 
         def ptr(t):
             return t.data_ptr() if t is not None else None
         self.call('power_vjp', C.byref(params), a.dim(), es // 2, ptr(a), strides(a), ptr(b), strides(b), ptr(grad_a),
-                  strides(grad_a), ptr(grad_b), strides(grad_b), _abi.i64arr(a.shape, 3), _abi.i64arr(start, 3),
-                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), kedges.data_ptr(),
+                  strides(grad_a), ptr(grad_b), strides(grad_b), _abi.i64arr(a.shape, 3),
+                  *_mesh_args(start, nmesh, boxsize), kedges.data_ptr(),
                   muedges.data_ptr() if muedges is not None else None, coef.data_ptr(), self.stream())
 
     # -- binned bispectrum ---------------------------------------------------
@@ -246,9 +257,9 @@ class HipBackend(object):
         es = o.element_size()
         ptrs = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
         self.call('bispec_shells', o.dim(), es // 2, len(outs), int(deconv_pow), int(bool(unit)),
-                  None if unit else a.data_ptr(), None if unit else _abi.i64arr([s * es for s in a.stride()], 3), ptrs,
-                  _abi.i64arr([s * es for s in o.stride()], 3), _abi.i64arr(o.shape, 3), _abi.i64arr(start, 3),
-                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), kedges.data_ptr(), self.stream())
+                  None if unit else a.data_ptr(), None if unit else _byte_strides(a), ptrs,
+                  _byte_strides(o), _abi.i64arr(o.shape, 3), *_mesh_args(start, nmesh, boxsize), kedges.data_ptr(),
+                  self.stream())
 
     def bispec_reduce(self, fields, triangles, acc, work=None):
         """acc[t] += sum over the cells of fields[i] * fields[j] * fields[l] for (i, j, l) = triangles[t]: real blocks
@@ -262,7 +273,7 @@ class HipBackend(object):
         if work is None:
             work = torch.empty(self.bispec_work(ntri, f.numel()), dtype=torch.float64, device=self.device)
         ptrs = (C.c_void_p * len(fields))(*[t.data_ptr() for t in fields])
-        self.call('bispec_reduce', f.dim(), es, len(fields), ptrs, _abi.i64arr([s * es for s in f.stride()], 3),
+        self.call('bispec_reduce', f.dim(), es, len(fields), ptrs, _byte_strides(f),
                   _abi.i64arr(f.shape, 3), ntri, triangles.data_ptr(), acc.data_ptr(), work.data_ptr(), work.numel(),
                   self.stream())
 
@@ -278,27 +289,25 @@ class HipBackend(object):
         """out = T(|k|) v over the local complex block v (pmx_apply_ktable; `table` a _abi.KTable whose x / y are
         float64 device arrays kept alive by the caller); out may be v"""
         es = v.element_size()
-        self.call('apply_ktable', C.byref(table), v.dim(), es // 2, v.data_ptr(), _abi.i64arr([s * es for s in v.stride()], 3),
-                  out.data_ptr(), _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(v.shape, 3),
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+        self.call('apply_ktable', C.byref(table), v.dim(), es // 2, v.data_ptr(), _byte_strides(v),
+                  out.data_ptr(), _byte_strides(out), _abi.i64arr(v.shape, 3),
+                  *_mesh_args(start, nmesh, boxsize), self.stream())
 
     def ktable_vjp(self, table, hermitian, field, v, start, nmesh, boxsize, grad):
         """grad[i] += sum_m w_m Re(conj(v_m) field_m) e_i(|k_m|) over the local complex blocks (pmx_ktable_vjp; grad:
         float64 device vector of table.n entries)"""
         es = field.element_size()
         self.call('ktable_vjp', C.byref(table), int(bool(hermitian)), field.dim(), es // 2, field.data_ptr(),
-                  _abi.i64arr([s * es for s in field.stride()], 3), v.data_ptr(),
-                  _abi.i64arr([s * es for s in v.stride()], 3), _abi.i64arr(field.shape, 3), _abi.i64arr(start, 3),
-                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), grad.data_ptr(), self.stream())
+                  _byte_strides(field), v.data_ptr(), _byte_strides(v), _abi.i64arr(field.shape, 3),
+                  *_mesh_args(start, nmesh, boxsize), grad.data_ptr(), self.stream())
 
     def apply_ktable_jvp(self, table, dy, v, out, start, nmesh, boxsize):
         """out = T'(|k|) v, the tangent of apply_ktable along the table values (pmx_apply_ktable_jvp; dy: float64
         device vector of table.n entries); out may be v"""
         es = v.element_size()
         self.call('apply_ktable_jvp', C.byref(table), dy.data_ptr(), v.dim(), es // 2, v.data_ptr(),
-                  _abi.i64arr([s * es for s in v.stride()], 3), out.data_ptr(),
-                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3),
-                  _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+                  _byte_strides(v), out.data_ptr(), _byte_strides(out), _abi.i64arr(v.shape, 3),
+                  *_mesh_args(start, nmesh, boxsize), self.stream())
 
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
@@ -308,9 +317,8 @@ class HipBackend(object):
         ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
         strides = _abi.i64arr([s * es for o in outs for s in (list(o.stride()) + [0] * 3)[:3]])
         flat = (C.c_int32 * (2 * n))(*[int(x) for p in pairs for x in p])
-        self.call('lpt_hessian', v.dim(), es // 2, v.data_ptr(), _abi.i64arr([s * es for s in v.stride()], 3), n, flat,
-                  ptrs, strides, _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3),
-                  _abi.f64arr(boxsize, 3), self.stream())
+        self.call('lpt_hessian', v.dim(), es // 2, v.data_ptr(), _byte_strides(v), n, flat,
+                  ptrs, strides, _abi.i64arr(v.shape, 3), *_mesh_args(start, nmesh, boxsize), self.stream())
 
     def lpt2_source(self, ins, out, scale):
         """out = scale * S(phi_ij) over real blocks: ins = the diagonal, then the off-diagonal components
@@ -319,7 +327,7 @@ class HipBackend(object):
         ptrs = (C.c_void_p * len(ins))(*[a.data_ptr() for a in ins])
         strides = _abi.i64arr([s * es for a in ins for s in (list(a.stride()) + [0] * 3)[:3]])
         self.call('lpt2_source', out.dim(), es, ptrs, strides, out.data_ptr(),
-                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3), float(scale),
+                  _byte_strides(out), _abi.i64arr(out.shape, 3), float(scale),
                   self.stream())
 
     @staticmethod
@@ -335,8 +343,8 @@ class HipBackend(object):
         ptrs, strides = self._ptr_set(ins, es)
         flat = (C.c_int32 * (2 * len(ins)))(*[int(x) for f in factors for x in f])
         self.call('lpt_contract', out.dim(), es // 2, len(ins), ptrs, strides, flat, int(bool(accumulate)),
-                  out.data_ptr(), _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3),
-                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), _abi.f64arr(boxsize, 3), self.stream())
+                  out.data_ptr(), _byte_strides(out), _abi.i64arr(out.shape, 3),
+                  *_mesh_args(start, nmesh, boxsize), self.stream())
 
     def lpt2_source_vjp(self, g, ins, outs, scale):
         """outs[p] = scale * g * dS / d ins[p] over real blocks, components in the order of lpt2_source
@@ -344,7 +352,7 @@ class HipBackend(object):
         es = g.element_size()
         ip, istr = self._ptr_set(ins, es)
         op, ostr = self._ptr_set(outs, es)
-        self.call('lpt2_source_vjp', g.dim(), es, g.data_ptr(), _abi.i64arr([s * es for s in g.stride()], 3), ip,
+        self.call('lpt2_source_vjp', g.dim(), es, g.data_ptr(), _byte_strides(g), ip,
                   istr, op, ostr, _abi.i64arr(g.shape, 3), float(scale), self.stream())
 
     def lpt2_source_jvp(self, ins, tangents, out, scale):
@@ -353,7 +361,7 @@ class HipBackend(object):
         ip, istr = self._ptr_set(ins, es)
         tp, tstr = self._ptr_set(tangents, es)
         self.call('lpt2_source_jvp', out.dim(), es, ip, istr, tp, tstr, out.data_ptr(),
-                  _abi.i64arr([s * es for s in out.stride()], 3), _abi.i64arr(out.shape, 3), float(scale),
+                  _byte_strides(out), _abi.i64arr(out.shape, 3), float(scale),
                   self.stream())
 
 

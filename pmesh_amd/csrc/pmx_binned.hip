@@ -2672,9 +2672,7 @@ static int halo_cells(int S)
 // workgroups of a launch over n units (the kernels loop over what is left)
 static unsigned grid_cap(int64_t n) { return (unsigned)(n < 65535 * 8 ? n : 65535 * 8); }
 
-// ---- launch dispatch: a runtime value becomes a compile-time tag, handed to a generic lambda --------------------------
-template <int V> using int_c = std::integral_constant<int, V>;
-template <typename T> struct type_c { using type = T; };
+// ---- launch dispatch: the tags and the other with_* helpers are in pmx_common.h ---------------------------------------
 // the window kind (anything that is not NNB, CIC or TSC is PCS)
 template <typename F> void with_kind(int kind, F &&f)
 {
@@ -2684,23 +2682,6 @@ template <typename F> void with_kind(int kind, F &&f)
     case PMX_TUNED_TSC: f(int_c<PMX_TUNED_TSC>{}); break;
     default: f(int_c<PMX_TUNED_PCS>{}); break;
     }
-}
-template <typename F> void with_bool(bool b, F &&f)
-{
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-// an element size of 8 or 4 bytes (positions, results)
-template <typename F> void with_elsize(int elsize, F &&f)
-{
-    if (elsize == 8) f(int_c<8>{});
-    else f(int_c<4>{});
-}
-// the canvas type from its element size
-template <typename F> void with_canvas(int elsize, F &&f)
-{
-    if (elsize == 8) f(type_c<double>{});
-    else f(type_c<float>{});
 }
 
 }  // namespace pmx

@@ -6,8 +6,8 @@
 // reads every shell field from HBM once per triangle it takes part in.
 //
 // shells_kernel streams: one read of the mode (none in unit mode), nb writes, one thread per mode in memory order.
-// |k| and the shell of a mode are computed statement for statement as pmx_power.hip computes them (tile_axis, mode_k,
-// find_bin of pmx_power_dev.h), so a mode lands in the same shell here and in pmx_power_project.
+// |k| and the shell of a mode are computed as pmx_power.hip computes them (k_divided and sinc_pow of pmx_block_dev.h,
+// the sum of mode_k, find_bin of pmx_power_dev.h), so a mode lands in the same shell here and in pmx_power_project.
 //
 // reduce_kernel: a workgroup of sixteen waves stages a chunk of 64 K cells x nb shells in LDS as doubles (the only
 // read of the fields; every thread loads, a cell for every second, fourth or eighth shell).  Then its lanes own cells
@@ -25,18 +25,14 @@
 #include <math.h>
 
 #include "pmx_common.h"
-#include "pmx_power_dev.h"
+#include "pmx_block_dev.h"
+#include "pmx_power_dev.h"   // find_bin, guess
 
 namespace pmx {
 
 // ---- shells ----------------------------------------------------------------------------------------------------------
 
 struct BShells {
-    int64_t shape[3], start[3], nmesh[3];     // logical order (axes beyond ndim: extent 1, N = 1)
-    int64_t sa[3], so[3];                     // byte strides of the input and of every output, logical order
-    double dw[3], nl_n[3], boxsize[3];        // 2 pi / N, N, L
-    int32_t on[3];                            // a mesh axis (not padding)
-    int32_t ax[3];                            // memory-order permutation: ax[2] varies fastest
     int32_t nb, deconv_pow, unit;
 };
 
@@ -44,67 +40,44 @@ struct BPtrs {
     char *p[PMX_BISPEC_MAX_SHELLS];
 };
 
-// k_d and sinc(w_d / 2)^deconv_pow of global index gi along logical axis d: tile_axis of pmx_power_dev.h
-__device__ __forceinline__ double axis_k(const BShells &g, int d, int64_t gi, double &sp)
-{
-    sp = 1;
-    if (!g.on[d]) return 0;
-    double s = (double)gi;
-    if (gi >= g.nmesh[d] / 2) s -= (double)g.nmesh[d];
-    const double w = s * g.dw[d];
-    const double k = (w * g.nl_n[d]) / g.boxsize[d];
-    if (g.deconv_pow) {
-        const double x = 0.5 * w;
-        double sn;
-        if (x < 1e-5 && x > -1e-5) { double x2 = x * x; sn = 1.0 - x2 / 6. + x2 * x2 / 120.; }
-        else sn = sin(x) / x;
-        sp = sn;
-        for (int e = 1; e < g.deconv_pow; e++) sp *= sn;
-    }
-    return k;
-}
-
 template <typename T>
-__global__ void __launch_bounds__(256) shells_kernel(BShells g, const char *__restrict__ a, BPtrs out,
-                                                     const double *__restrict__ kedges)
+__global__ void __launch_bounds__(256) shells_kernel(BlockGeom g, BShells p, const char *__restrict__ a, BlockStr as,
+                                                     BPtrs out, BlockStr os, const double *__restrict__ kedges)
 {
     __shared__ double ke[PMX_BISPEC_MAX_SHELLS + 1];
-    for (int i = threadIdx.x; i <= g.nb; i += 256) ke[i] = kedges[i];
+    for (int i = threadIdx.x; i <= p.nb; i += 256) ke[i] = kedges[i];
     __syncthreads();
-    const int nb = g.nb;
+    const int nb = p.nb;
     const double ke0 = ke[0], kinv = nb / (ke[nb] - ke[0]);
-    const uint32_t n2 = (uint32_t)g.shape[g.ax[2]], inner = (uint32_t)g.shape[g.ax[1]] * n2;
-    for (int64_t i0 = blockIdx.y; i0 < g.shape[g.ax[0]]; i0 += gridDim.y)
-        for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < inner; q += gridDim.x * 256) {
-            const uint32_t i1 = q / n2;
-            const int64_t v0 = i0, v1 = i1, v2 = q - i1 * n2;
-            int64_t idx[3];
+    PMX_BLOCK_LOOP(g) {
+        int64_t idx[3];
+        block_index(g, i0_, q_, idx);
+        double kk[3], ww[3];
+        const double kmag = sqrt(wavevector<true>(g, idx, kk, ww));
+        int j = -1;
+        if (kmag >= ke0 && kmag < ke[nb]) j = find_bin(ke, nb, kmag, guess(kmag, ke0, kinv));
+        double re = 1, im = 0;
+        if (!p.unit && j >= 0) {
+            CLoad<T>::get(a + as.off(idx), re, im);
+            if (p.deconv_pow) {
 #pragma unroll
-            for (int d = 0; d < 3; d++) idx[d] = (g.ax[0] == d) ? v0 : ((g.ax[1] == d) ? v1 : v2);
-            double kk[3], sp[3];
-#pragma unroll
-            for (int d = 0; d < 3; d++) kk[d] = axis_k(g, d, g.start[d] + idx[d], sp[d]);
-            const double kmag = sqrt((kk[0] * kk[0] + kk[1] * kk[1]) + kk[2] * kk[2]);
-            int j = -1;
-            if (kmag >= ke0 && kmag < ke[nb]) j = find_bin(ke, nb, kmag, guess(kmag, ke0, kinv));
-            double re = 1, im = 0;
-            if (!g.unit && j >= 0) {
-                Cplx<T>::load(a + (idx[0] * g.sa[0] + idx[1] * g.sa[1] + idx[2] * g.sa[2]), re, im);
-                if (g.deconv_pow) {
-#pragma unroll
-                    for (int d = 0; d < 3; d++) {
-                        re /= sp[d];
-                        im /= sp[d];
-                    }
+                for (int d = 0; d < 3; d++) {
+                    if (d >= g.ndim) continue;
+                    const double sp = sinc_pow(ww[d], p.deconv_pow);
+                    re /= sp;
+                    im /= sp;
                 }
             }
-            const int64_t off = idx[0] * g.so[0] + idx[1] * g.so[1] + idx[2] * g.so[2];
-            for (int s = 0; s < nb; s++) {
-                const bool mine = s == j;
-                Cplx<T>::store(out.p[s] + off, mine ? re : 0.0, mine ? im : 0.0);
-            }
         }
+        const int64_t off = os.off(idx);
+        for (int s = 0; s < nb; s++) {
+            const bool mine = s == j;
+            CLoad<T>::put(out.p[s] + off, mine ? re : 0.0, mine ? im : 0.0);
+        }
+    }
 }
+
+#undef PMX_BLOCK_LOOP
 
 // ---- reduce ----------------------------------------------------------------------------------------------------------
 
@@ -243,12 +216,6 @@ __global__ void __launch_bounds__(256) sum_kernel(const double *__restrict__ par
     acc[t] += s;
 }
 
-template <typename T, int K>
-static void launch_reduce(int nwg, hipStream_t st, const BReduce &g, const BFields &f, const int32_t *tri, double *part)
-{
-    reduce_kernel<T, K><<<nwg, BWG, sizeof(double) * g.nb * 64 * K, st>>>(g, f, tri, part);
-}
-
 // cells per lane for nb shells: the staged chunk takes up to 64 KB of LDS (two workgroups per CU)
 static int cells_per_lane(int nb) { return nb <= 16 ? 8 : (nb <= 32 ? 4 : 2); }
 
@@ -268,44 +235,25 @@ extern "C" int pmx_bispec_shells(int32_t ndim, int32_t elsize, int32_t nb, int32
     PMX_REQUIRE(nb >= 1, PMX_EINVAL, "nb must be >= 1");
     PMX_REQUIRE(nb <= PMX_BISPEC_MAX_SHELLS, PMX_EUNSUPPORTED, "nb above PMX_BISPEC_MAX_SHELLS");
     PMX_REQUIRE(deconv_pow >= 0, PMX_EINVAL, "deconv_pow must be >= 0");
-    BShells g;
+    // memory order by decreasing stride of the outputs, axes of extent 1 slowest
+    const BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides, AXES_UNIT_SLOWEST);
+    for (int d = 0; d < 3; d++) PMX_REQUIRE(g.shape[d] >= 0 && g.nmesh[d] >= 1, PMX_EINVAL, "bad shape");
+    const BShells p = {nb, deconv_pow, unit ? 1 : 0};
     BPtrs o;
-    for (int d = 0; d < 3; d++) {
-        const bool on = d < ndim;
-        g.shape[d] = on ? shape[d] : 1;
-        g.start[d] = on ? start[d] : 0;
-        g.nmesh[d] = on ? nmesh[d] : 1;
-        g.sa[d] = on && !unit ? a_strides[d] : 0;
-        g.so[d] = on ? out_strides[d] : 0;
-        g.dw[d] = 2 * M_PI / g.nmesh[d];
-        g.nl_n[d] = (double)g.nmesh[d];
-        g.boxsize[d] = on ? boxsize[d] : 1.0;
-        g.on[d] = on;
-        PMX_REQUIRE(g.shape[d] >= 0 && g.nmesh[d] >= 1, PMX_EINVAL, "bad shape");
-    }
-    g.nb = nb;
-    g.deconv_pow = deconv_pow;
-    g.unit = unit ? 1 : 0;
     for (int s = 0; s < PMX_BISPEC_MAX_SHELLS; s++) {
         o.p[s] = s < nb ? (char *)out[s] : nullptr;
         PMX_REQUIRE(s >= nb || o.p[s], PMX_EINVAL, "output pointer");
     }
-    if (g.shape[0] * g.shape[1] * g.shape[2] == 0) return PMX_OK;
-    // memory order by decreasing stride of the outputs, axes of extent 1 slowest
-    int ax[3] = {0, 1, 2};
-    for (int x = 0; x < 3; x++)
-        for (int y = x + 1; y < 3; y++) {
-            const bool ux = g.shape[ax[x]] == 1, uy = g.shape[ax[y]] == 1;
-            const bool swap = ux != uy ? uy : llabs(g.so[ax[x]]) < llabs(g.so[ax[y]]);
-            if (swap) { int t = ax[x]; ax[x] = ax[y]; ax[y] = t; }
-        }
-    for (int m = 0; m < 3; m++) g.ax[m] = ax[m];
-    const int64_t inner = g.shape[ax[1]] * g.shape[ax[2]], n0 = g.shape[ax[0]];
-    PMX_REQUIRE(inner < (1ll << 31), PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
-    dim3 grid((unsigned)((inner + 255) / 256), (unsigned)(n0 < 65535 ? n0 : 65535));
+    dim3 grid;
+    const int r = grid_of(g, grid);
+    PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
+    if (r == 0) return PMX_OK;
+    const BlockStr as = make_str(ndim, unit ? nullptr : a_strides), os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
-    if (elsize == 8) shells_kernel<double><<<grid, 256, 0, st>>>(g, (const char *)a, o, kedges);
-    else shells_kernel<float><<<grid, 256, 0, st>>>(g, (const char *)a, o, kedges);
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        shells_kernel<T><<<grid, 256, 0, st>>>(g, p, (const char *)a, as, o, os, kedges);
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -347,15 +295,16 @@ extern "C" int pmx_bispec_reduce(int32_t ndim, int32_t elsize, int32_t nb, const
     if (nwg > BMAX_WG) nwg = BMAX_WG;
     if (nwg > g.nchunks) nwg = g.nchunks;
     hipStream_t st = (hipStream_t)stream;
-    if (elsize == 8) {
-        if (K == 8) launch_reduce<double, 8>((int)nwg, st, g, f, triangles, part);
-        else if (K == 4) launch_reduce<double, 4>((int)nwg, st, g, f, triangles, part);
-        else launch_reduce<double, 2>((int)nwg, st, g, f, triangles, part);
-    } else {
-        if (K == 8) launch_reduce<float, 8>((int)nwg, st, g, f, triangles, part);
-        else if (K == 4) launch_reduce<float, 4>((int)nwg, st, g, f, triangles, part);
-        else launch_reduce<float, 2>((int)nwg, st, g, f, triangles, part);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        auto launch = [&](auto k) {
+            constexpr int KC = decltype(k)::value;
+            reduce_kernel<T, KC><<<(int)nwg, BWG, sizeof(double) * g.nb * 64 * KC, st>>>(g, f, triangles, part);
+        };
+        if (K == 8) launch(int_c<8>{});
+        else if (K == 4) launch(int_c<4>{});
+        else launch(int_c<2>{});
+    });
     PMX_HIP_CHECK(hipGetLastError());
     sum_kernel<<<(ntri + 255) / 256, 256, 0, st>>>(part, (int)nwg, ntri, acc);
     PMX_HIP_CHECK(hipGetLastError());

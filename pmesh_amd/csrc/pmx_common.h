@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/pmesh_amd.h"
 
@@ -77,14 +78,32 @@ template <int PE> __device__ __forceinline__ double pos_get(const DVec &pos, int
     return PE == 8 ? *(const double *)q : (double)*(const float *)q;
 }
 
-// The wavenumber of global index gi along an axis of n cells: w = 2 pi / n (gi - n [gi >= n / 2]), k = w n / L, with
-// dw = 2 pi / n and nl = n / L — the sequence of roundings of transfer_kernel (pmx_transfer.hip) and ComplexField.x.
-__device__ __forceinline__ double wavenumber(int64_t gi, int64_t n, double dw, double nl)
+// ---- launch dispatch: a runtime value becomes a compile-time tag, handed to a generic lambda --------------------------
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename T> struct type_c { using type = T; };
+template <typename F> void with_bool(bool b, F &&f)
 {
-    double wi = (double)gi;
-    if (gi >= n / 2) wi -= n;
-    wi *= dw;
-    return wi * nl;
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// an element size of 8 or 4 bytes (positions, results)
+template <typename F> void with_elsize(int elsize, F &&f)
+{
+    if (elsize == 8) f(int_c<8>{});
+    else f(int_c<4>{});
+}
+// the canvas (field) type from its element size
+template <typename F> void with_canvas(int elsize, F &&f)
+{
+    if (elsize == 8) f(type_c<double>{});
+    else f(type_c<float>{});
+}
+// a small count n in 1 .. N (clamped to that range)
+template <int N, typename F> void with_count(int n, F &&f)
+{
+    if constexpr (N == 1) f(int_c<1>{});
+    else if (n >= N) f(int_c<N>{});
+    else with_count<N - 1>(n, f);
 }
 
 inline DVec dvec(const pmx_vec *v)

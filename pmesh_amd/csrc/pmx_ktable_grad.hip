@@ -3,7 +3,7 @@
 //
 // A caller of the reference fits band powers or transfer-function nodes through numpy.interp inside Field.apply and has
 // no gradient of it at all.  Both kernels stream over the complex block like ktable_kernel, wavenumbers recomputed from
-// the index and the table searched by the same table_find (pmx_lpt_dev.h).
+// the index and the table searched by the same table_find (pmx_block_dev.h).
 //   ktable_vjp:  reads in and v once; a mode between two table entries adds its two interpolation weights times
 //                w Re(conj(v) in) into a copy of the table's sums in LDS (n doubles, sized to the table).  Neighbouring
 //                modes of a wave mostly share an entry, and LDS atomics on one address run one lane after another: a
@@ -14,7 +14,7 @@
 #include <math.h>
 
 #include "pmx_common.h"
-#include "pmx_lpt_dev.h"
+#include "pmx_block_dev.h"
 
 namespace pmx {
 
@@ -31,8 +31,8 @@ __device__ __forceinline__ double run_sum(double v, int lane, int end)
 }
 
 template <typename T, bool LOG>
-__global__ void __launch_bounds__(256) ktable_vjp_kernel(pmx_ktable t, LGeom g, int hermitian, const char *in, LStr is,
-                                                         const char *v, LStr vs, double *__restrict__ grad)
+__global__ void __launch_bounds__(256) ktable_vjp_kernel(pmx_ktable t, BlockGeom g, int hermitian, const char *in, BlockStr is,
+                                                         const char *v, BlockStr vs, double *__restrict__ grad)
 {
     extern __shared__ double tab[];                 // t.n sums
     for (int i = threadIdx.x; i < t.n; i += 256) tab[i] = 0;
@@ -104,10 +104,10 @@ __global__ void __launch_bounds__(256) ktable_vjp_kernel(pmx_ktable t, LGeom g, 
 }
 
 template <typename T, bool LOG>
-__global__ void __launch_bounds__(256) ktable_jvp_kernel(pmx_ktable t, const double *__restrict__ dy, LGeom g,
-                                                         const char *in, LStr is, char *out, LStr os)
+__global__ void __launch_bounds__(256) ktable_jvp_kernel(pmx_ktable t, const double *__restrict__ dy, BlockGeom g,
+                                                         const char *in, BlockStr is, char *out, BlockStr os)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double kk[3];
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(256) ktable_jvp_kernel(pmx_ktable t, const dou
     }
 }
 
-#undef PMX_LPT_LOOP
+#undef PMX_BLOCK_LOOP
 
 }  // namespace pmx
 
@@ -156,7 +156,7 @@ extern "C" int pmx_ktable_vjp(const pmx_ktable *t, int32_t hermitian, int32_t nd
     PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
     PMX_REQUIRE(t->n >= 2 && t->n <= PMX_KTABLE_MAX, PMX_EUNSUPPORTED, "table of 2 .. PMX_KTABLE_MAX entries");
     PMX_REQUIRE(t->x && (t->y || !t->loglog), PMX_EINVAL, "table pointers");
-    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, in_strides);
+    BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, in_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
@@ -165,18 +165,17 @@ extern "C" int pmx_ktable_vjp(const pmx_ktable *t, int32_t hermitian, int32_t nd
     if (grid.x > (unsigned)KV_BLOCKS) grid.x = KV_BLOCKS;
     const unsigned ny = KV_BLOCKS / grid.x;
     if (grid.y > ny) grid.y = ny;
-    const LStr is = make_str(ndim, in_strides), vs = make_str(ndim, v_strides);
+    const BlockStr is = make_str(ndim, in_strides), vs = make_str(ndim, v_strides);
     hipStream_t st = (hipStream_t)stream;
     const char *a = (const char *)in, *b = (const char *)v;
     const size_t lds = sizeof(double) * (size_t)t->n;
     const int h = hermitian ? 1 : 0;
-    if (elsize == 8) {
-        if (t->loglog) ktable_vjp_kernel<double, true><<<grid, 256, lds, st>>>(*t, g, h, a, is, b, vs, grad);
-        else ktable_vjp_kernel<double, false><<<grid, 256, lds, st>>>(*t, g, h, a, is, b, vs, grad);
-    } else {
-        if (t->loglog) ktable_vjp_kernel<float, true><<<grid, 256, lds, st>>>(*t, g, h, a, is, b, vs, grad);
-        else ktable_vjp_kernel<float, false><<<grid, 256, lds, st>>>(*t, g, h, a, is, b, vs, grad);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(t->loglog != 0, [&](auto lg) {
+            ktable_vjp_kernel<T, lg><<<grid, 256, lds, st>>>(*t, g, h, a, is, b, vs, grad);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -191,22 +190,21 @@ extern "C" int pmx_apply_ktable_jvp(const pmx_ktable *t, const double *dy, int32
     PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
     PMX_REQUIRE(t->n >= 2 && t->n <= PMX_KTABLE_MAX, PMX_EUNSUPPORTED, "table of 2 .. PMX_KTABLE_MAX entries");
     PMX_REQUIRE(t->x && (t->y || !t->loglog), PMX_EINVAL, "table pointers");
-    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
+    BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
     if (r == 0) return PMX_OK;
-    const LStr is = make_str(ndim, in_strides), os = make_str(ndim, out_strides);
+    const BlockStr is = make_str(ndim, in_strides), os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
     const char *a = (const char *)in;
     char *b = (char *)out;
-    if (elsize == 8) {
-        if (t->loglog) ktable_jvp_kernel<double, true><<<grid, 256, 0, st>>>(*t, dy, g, a, is, b, os);
-        else ktable_jvp_kernel<double, false><<<grid, 256, 0, st>>>(*t, dy, g, a, is, b, os);
-    } else {
-        if (t->loglog) ktable_jvp_kernel<float, true><<<grid, 256, 0, st>>>(*t, dy, g, a, is, b, os);
-        else ktable_jvp_kernel<float, false><<<grid, 256, 0, st>>>(*t, dy, g, a, is, b, os);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(t->loglog != 0, [&](auto lg) {
+            ktable_jvp_kernel<T, lg><<<grid, 256, 0, st>>>(*t, dy, g, a, is, b, os);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }

@@ -6,32 +6,33 @@
 // examples/nbody.py:245-282) and the chain of per-component apply calls and products of the reference's
 // nbody/genic.py:121-166.  All three kernels stream: one read and one write per element (the Hessian kernel one read
 // and up to three writes, the source kernel one read of each of its 3 or 6 inputs), one thread per element in memory
-// order, wavenumbers recomputed from the index with the roundings of transfer_kernel (pmx_common.h: wavenumber).
+// order (PMX_BLOCK_LOOP), wavenumbers recomputed from the index with the roundings of transfer_kernel
+// (pmx_block_dev.h: k_scaled).
 // The table of pmx_apply_ktable stays in device memory: a wave's neighbouring modes walk the same few lines of it,
 // which the L1 / L2 serve, and no workgroup pays for loading a whole table into LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "pmx_common.h"
-#include "pmx_lpt_dev.h"
+#include "pmx_block_dev.h"
 
 namespace pmx {
 
 struct HOut {
     char *p[3];
-    LStr s[3];
+    BlockStr s[3];
     int32_t i[3], j[3];
 };
 
 struct SIn {
     const char *p[6];
-    LStr s[6];
+    BlockStr s[6];
 };
 
 template <typename T, bool LOG>
-__global__ void __launch_bounds__(256) ktable_kernel(pmx_ktable t, LGeom g, const char *in, LStr is, char *out, LStr os)
+__global__ void __launch_bounds__(256) ktable_kernel(pmx_ktable t, BlockGeom g, const char *in, BlockStr is, char *out, BlockStr os)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double kk[3];
@@ -49,9 +50,9 @@ __global__ void __launch_bounds__(256) ktable_kernel(pmx_ktable t, LGeom g, cons
 }
 
 template <typename T, int NOUT>
-__global__ void __launch_bounds__(256) hessian_kernel(LGeom g, const char *in, LStr is, HOut o)
+__global__ void __launch_bounds__(256) hessian_kernel(BlockGeom g, const char *in, BlockStr is, HOut o)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double kk[3];
@@ -72,9 +73,9 @@ template <typename T> __device__ __forceinline__ double rget(const SIn &a, int q
 }
 
 template <typename T, int ND>
-__global__ void __launch_bounds__(256) lpt2_source_kernel(LGeom g, SIn a, char *out, LStr os, double scale)
+__global__ void __launch_bounds__(256) lpt2_source_kernel(BlockGeom g, SIn a, char *out, BlockStr os, double scale)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double s;
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(256) lpt2_source_kernel(LGeom g, SIn a, char *
     }
 }
 
-#undef PMX_LPT_LOOP
+#undef PMX_BLOCK_LOOP
 
 }  // namespace pmx
 
@@ -110,22 +111,21 @@ extern "C" int pmx_apply_ktable(const pmx_ktable *t, int32_t ndim, int32_t elsiz
     PMX_REQUIRE(elsize == 4 || elsize == 8, PMX_EINVAL, "elsize must be 4 or 8");
     PMX_REQUIRE(t->n >= 2 && t->n <= PMX_KTABLE_MAX, PMX_EUNSUPPORTED, "table of 2 .. PMX_KTABLE_MAX entries");
     PMX_REQUIRE(t->x && t->y, PMX_EINVAL, "table pointers");
-    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
+    BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
     if (r == 0) return PMX_OK;
-    const LStr is = make_str(ndim, in_strides), os = make_str(ndim, out_strides);
+    const BlockStr is = make_str(ndim, in_strides), os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
     const char *a = (const char *)in;
     char *b = (char *)out;
-    if (elsize == 8) {
-        if (t->loglog) ktable_kernel<double, true><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
-        else ktable_kernel<double, false><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
-    } else {
-        if (t->loglog) ktable_kernel<float, true><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
-        else ktable_kernel<float, false><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(t->loglog != 0, [&](auto lg) {
+            ktable_kernel<T, lg><<<grid, 256, 0, st>>>(*t, g, a, is, b, os);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -149,23 +149,18 @@ extern "C" int pmx_lpt_hessian(int32_t ndim, int32_t elsize, const void *in, con
         PMX_REQUIRE(!on || (o.p[p] && o.i[p] >= 0 && o.i[p] < ndim && o.j[p] >= 0 && o.j[p] < ndim), PMX_EINVAL,
                     "output pointer or pair out of range");
     }
-    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, in_strides);
+    BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, in_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
     if (r == 0) return PMX_OK;
-    const LStr is = make_str(ndim, in_strides);
+    const BlockStr is = make_str(ndim, in_strides);
     hipStream_t st = (hipStream_t)stream;
     const char *a = (const char *)in;
-    if (elsize == 8) {
-        if (nout == 1) hessian_kernel<double, 1><<<grid, 256, 0, st>>>(g, a, is, o);
-        else if (nout == 2) hessian_kernel<double, 2><<<grid, 256, 0, st>>>(g, a, is, o);
-        else hessian_kernel<double, 3><<<grid, 256, 0, st>>>(g, a, is, o);
-    } else {
-        if (nout == 1) hessian_kernel<float, 1><<<grid, 256, 0, st>>>(g, a, is, o);
-        else if (nout == 2) hessian_kernel<float, 2><<<grid, 256, 0, st>>>(g, a, is, o);
-        else hessian_kernel<float, 3><<<grid, 256, 0, st>>>(g, a, is, o);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_count<3>(nout, [&](auto n) { hessian_kernel<T, n><<<grid, 256, 0, st>>>(g, a, is, o); });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -184,21 +179,20 @@ extern "C" int pmx_lpt2_source(int32_t ndim, int32_t elsize, const void *const *
         a.s[q] = make_str(ndim, on ? in_strides + 3 * q : out_strides);
         PMX_REQUIRE(!on || a.p[q], PMX_EINVAL, "input pointer");
     }
-    LGeom g = make_geom(ndim, shape, nullptr, nullptr, nullptr, out_strides);
+    BlockGeom g = make_geom(ndim, shape, nullptr, nullptr, nullptr, out_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 elements");
     if (r == 0) return PMX_OK;
-    const LStr os = make_str(ndim, out_strides);
+    const BlockStr os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
     char *b = (char *)out;
-    if (elsize == 8) {
-        if (ndim == 2) lpt2_source_kernel<double, 2><<<grid, 256, 0, st>>>(g, a, b, os, scale);
-        else lpt2_source_kernel<double, 3><<<grid, 256, 0, st>>>(g, a, b, os, scale);
-    } else {
-        if (ndim == 2) lpt2_source_kernel<float, 2><<<grid, 256, 0, st>>>(g, a, b, os, scale);
-        else lpt2_source_kernel<float, 3><<<grid, 256, 0, st>>>(g, a, b, os, scale);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(ndim == 2, [&](auto two) {
+            lpt2_source_kernel<T, two ? 2 : 3><<<grid, 256, 0, st>>>(g, a, b, os, scale);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }

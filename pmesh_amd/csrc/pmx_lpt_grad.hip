@@ -4,7 +4,7 @@
 // Replaces the chains of the reference's pmesh/abopt.py (the transfer vjp of apply_transfer and the c2r / r2c vjps
 // composed per component) that a caller of Field.apply would spell for the gradient of 2LPT.  The three kernels stream
 // like those of pmx_lpt.hip: one thread per element in memory order, wavenumbers recomputed from the index
-// (pmx_common.h: wavenumber), double arithmetic over f4 / f8 storage.
+// (pmx_block_dev.h: k_scaled), double arithmetic over f4 / f8 storage.
 //   contract:   out = (accumulate ? out : 0) + sum_c f_c(k) in_c over 1..6 spectra, f_c = k_i k_j / k^2 (a Hessian
 //               factor) or -i k_d / k^2 (the conjugate of the gradient factor of Transfer.dx1)
 //   source_vjp: the 3 or 6 products scale g dQ/dphi_p, written over the Hessian components when asked
@@ -13,30 +13,30 @@
 #include <math.h>
 
 #include "pmx_common.h"
-#include "pmx_lpt_dev.h"
+#include "pmx_block_dev.h"
 
 namespace pmx {
 
 struct CIn {
     const char *p[6];
-    LStr s[6];
+    BlockStr s[6];
     int32_t a[6], b[6];     // factor c: k_a k_b / k^2 (b >= 0) or -i k_a / k^2 (b < 0)
 };
 
 struct RSet {
     const char *p[6];
-    LStr s[6];
+    BlockStr s[6];
 };
 
 struct WSet {
     char *p[6];
-    LStr s[6];
+    BlockStr s[6];
 };
 
 template <typename T, int NIN>
-__global__ void __launch_bounds__(256) contract_kernel(LGeom g, CIn in, char *out, LStr os, int accumulate)
+__global__ void __launch_bounds__(256) contract_kernel(BlockGeom g, CIn in, char *out, BlockStr os, int accumulate)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double kk[3];
@@ -74,10 +74,10 @@ template <typename T> __device__ __forceinline__ void rstore(const WSet &a, int 
 
 // every input of the element is read before the first write: an output may be its own input
 template <typename T, int ND>
-__global__ void __launch_bounds__(256) lpt2_source_vjp_kernel(LGeom g, const char *gp, LStr gs, RSet h, WSet o,
+__global__ void __launch_bounds__(256) lpt2_source_vjp_kernel(BlockGeom g, const char *gp, BlockStr gs, RSet h, WSet o,
                                                               double scale)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         const double a = scale * (double)*(const T *)(gp + gs.off(idx));
@@ -100,10 +100,10 @@ __global__ void __launch_bounds__(256) lpt2_source_vjp_kernel(LGeom g, const cha
 }
 
 template <typename T, int ND>
-__global__ void __launch_bounds__(256) lpt2_source_jvp_kernel(LGeom g, RSet h, RSet t, char *out, LStr os,
+__global__ void __launch_bounds__(256) lpt2_source_jvp_kernel(BlockGeom g, RSet h, RSet t, char *out, BlockStr os,
                                                               double scale)
 {
-    PMX_LPT_LOOP(g) {
+    PMX_BLOCK_LOOP(g) {
         int64_t idx[3];
         block_index(g, i0_, q_, idx);
         double s;
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256) lpt2_source_jvp_kernel(LGeom g, RSet h, R
     }
 }
 
-#undef PMX_LPT_LOOP
+#undef PMX_BLOCK_LOOP
 
 }  // namespace pmx
 
@@ -152,36 +152,25 @@ extern "C" int pmx_lpt_contract(int32_t ndim, int32_t elsize, int32_t nin, const
                     "input pointer or factor out of range");
         if (on && c.b[q] < 0) c.b[q] = -1;
     }
-    LGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
+    BlockGeom g = make_geom(ndim, shape, start, nmesh, boxsize, out_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 modes");
     if (r == 0) return PMX_OK;
-    const LStr os = make_str(ndim, out_strides);
+    const BlockStr os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
     char *o = (char *)out;
     const int acc = accumulate ? 1 : 0;
-#define PMX_CONTRACT(T)                                                                                            \
-    switch (nin) {                                                                                                 \
-    case 1: contract_kernel<T, 1><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                  \
-    case 2: contract_kernel<T, 2><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                  \
-    case 3: contract_kernel<T, 3><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                  \
-    case 4: contract_kernel<T, 4><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                  \
-    case 5: contract_kernel<T, 5><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                  \
-    default: contract_kernel<T, 6><<<grid, 256, 0, st>>>(g, c, o, os, acc); break;                                 \
-    }
-    if (elsize == 8) {
-        PMX_CONTRACT(double)
-    } else {
-        PMX_CONTRACT(float)
-    }
-#undef PMX_CONTRACT
+    with_canvas(elsize, [&](auto tc) {
+        using T = typename decltype(tc)::type;
+        with_count<6>(nin, [&](auto n) { contract_kernel<T, n><<<grid, 256, 0, st>>>(g, c, o, os, acc); });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
 
 static int real_set(int32_t ndim, int n, const void *const *p, const int64_t *strides, const int64_t *fallback,
-                    const char **ptr, LStr *str)
+                    const char **ptr, BlockStr *str)
 {
     for (int q = 0; q < 6; q++) {
         const bool on = q < n;
@@ -207,21 +196,20 @@ extern "C" int pmx_lpt2_source_vjp(int32_t ndim, int32_t elsize, const void *g, 
     PMX_REQUIRE(real_set(ndim, n, (const void *const *)out, out_strides, g_strides, op, o.s), PMX_EINVAL,
                 "output pointer");
     for (int q = 0; q < 6; q++) o.p[q] = (char *)op[q];
-    LGeom geo = make_geom(ndim, shape, nullptr, nullptr, nullptr, g_strides);
+    BlockGeom geo = make_geom(ndim, shape, nullptr, nullptr, nullptr, g_strides);
     dim3 grid;
     const int r = grid_of(geo, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 elements");
     if (r == 0) return PMX_OK;
-    const LStr gs = make_str(ndim, g_strides);
+    const BlockStr gs = make_str(ndim, g_strides);
     hipStream_t st = (hipStream_t)stream;
     const char *gp = (const char *)g;
-    if (elsize == 8) {
-        if (ndim == 2) lpt2_source_vjp_kernel<double, 2><<<grid, 256, 0, st>>>(geo, gp, gs, h, o, scale);
-        else lpt2_source_vjp_kernel<double, 3><<<grid, 256, 0, st>>>(geo, gp, gs, h, o, scale);
-    } else {
-        if (ndim == 2) lpt2_source_vjp_kernel<float, 2><<<grid, 256, 0, st>>>(geo, gp, gs, h, o, scale);
-        else lpt2_source_vjp_kernel<float, 3><<<grid, 256, 0, st>>>(geo, gp, gs, h, o, scale);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(ndim == 2, [&](auto two) {
+            lpt2_source_vjp_kernel<T, two ? 2 : 3><<<grid, 256, 0, st>>>(geo, gp, gs, h, o, scale);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -237,21 +225,20 @@ extern "C" int pmx_lpt2_source_jvp(int32_t ndim, int32_t elsize, const void *con
     RSet h, t;
     PMX_REQUIRE(real_set(ndim, n, in, in_strides, out_strides, h.p, h.s), PMX_EINVAL, "input pointer");
     PMX_REQUIRE(real_set(ndim, n, tangent, tangent_strides, out_strides, t.p, t.s), PMX_EINVAL, "tangent pointer");
-    LGeom g = make_geom(ndim, shape, nullptr, nullptr, nullptr, out_strides);
+    BlockGeom g = make_geom(ndim, shape, nullptr, nullptr, nullptr, out_strides);
     dim3 grid;
     const int r = grid_of(g, grid);
     PMX_REQUIRE(r >= 0, PMX_EUNSUPPORTED, "plane of more than 2^31 elements");
     if (r == 0) return PMX_OK;
-    const LStr os = make_str(ndim, out_strides);
+    const BlockStr os = make_str(ndim, out_strides);
     hipStream_t st = (hipStream_t)stream;
     char *b = (char *)out;
-    if (elsize == 8) {
-        if (ndim == 2) lpt2_source_jvp_kernel<double, 2><<<grid, 256, 0, st>>>(g, h, t, b, os, scale);
-        else lpt2_source_jvp_kernel<double, 3><<<grid, 256, 0, st>>>(g, h, t, b, os, scale);
-    } else {
-        if (ndim == 2) lpt2_source_jvp_kernel<float, 2><<<grid, 256, 0, st>>>(g, h, t, b, os, scale);
-        else lpt2_source_jvp_kernel<float, 3><<<grid, 256, 0, st>>>(g, h, t, b, os, scale);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(ndim == 2, [&](auto two) {
+            lpt2_source_jvp_kernel<T, two ? 2 : 3><<<grid, 256, 0, st>>>(g, h, t, b, os, scale);
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }

@@ -113,9 +113,9 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
                 ar[u] = ai[u] = br[u] = bi[u] = 0;
                 if (r < r1 && lane_on) {
                     const int i0 = r / ext[1], i1 = r - i0 * ext[1];
-                    Cplx<T>::load(a + (o[0] + i0) * g.sa[0] + (o[1] + i1) * g.sa[1] + offa2, ar[u], ai[u]);
+                    CLoad<T>::get(a + (o[0] + i0) * g.sa[0] + (o[1] + i1) * g.sa[1] + offa2, ar[u], ai[u]);
                     if (P.cross)
-                        Cplx<T>::load(b + (o[0] + i0) * g.sb[0] + (o[1] + i1) * g.sb[1] + offb2, br[u], bi[u]);
+                        CLoad<T>::get(b + (o[0] + i0) * g.sb[0] + (o[1] + i1) * g.sb[1] + offb2, br[u], bi[u]);
                 }
             }
 #pragma unroll
@@ -222,13 +222,6 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
     }
 }
 
-template <typename T, bool MU, bool POLES>
-static void launch(dim3 grid, size_t lds, hipStream_t st, const PParams &P, const PGeom &g, const void *a,
-                   const void *b, const double *ke, const double *me, double *acc)
-{
-    power_kernel<T, MU, POLES><<<grid, PBLOCK, lds, st>>>(P, g, (const char *)a, (const char *)b, ke, me, acc);
-}
-
 }  // namespace pmx
 
 using namespace pmx;
@@ -250,17 +243,14 @@ extern "C" int pmx_power_project(const pmx_power *p, int32_t ndim, int32_t elsiz
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)ntiles);
     const bool mu = p->nmu > 0, poles = p->npoles > 0;
-    if (elsize == 8) {
-        if (mu && poles) launch<double, true, true>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else if (mu) launch<double, true, false>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else if (poles) launch<double, false, true>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else launch<double, false, false>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-    } else {
-        if (mu && poles) launch<float, true, true>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else if (mu) launch<float, true, false>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else if (poles) launch<float, false, true>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-        else launch<float, false, false>(grid, lds, s, P, g, a, b, kedges, muedges, acc);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(mu, [&](auto m) {
+            with_bool(poles, [&](auto pl) {
+                power_kernel<T, m, pl><<<grid, PBLOCK, lds, s>>>(P, g, (const char *)a, (const char *)b, kedges, muedges, acc);
+            });
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }

@@ -1,13 +1,15 @@
 // pmx_power_dev.h — what the binned power spectrum (pmx_power.hip) and its adjoint (pmx_power_grad.hip) share, so that
 // both land every mode in the same bin: the tile geometry, the per-axis wavenumber and sinc tables of a tile with the
 // extreme |k_d| of its index box, the window search over the k edges, find_bin / guess / mu_bin, the Legendre
-// recurrence, complex loads of f4 / f8 storage into double, and the host side that orders the axes and sizes the LDS
-// window.  The arithmetic is the forward's, statement for statement (-ffp-contract=off keeps its roundings).
+// recurrence, and the host side that orders the axes and sizes the LDS window.  The wavenumber (k_divided), the sinc
+// power, the complex loads and the axis-order rule come from pmx_block_dev.h.  The arithmetic is the forward's,
+// statement for statement (-ffp-contract=off keeps its roundings).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "pmx_common.h"
+#include "pmx_block_dev.h"
 
 namespace pmx {
 
@@ -93,29 +95,6 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
-template <typename T> struct Cplx;
-template <> struct Cplx<double> {
-    static __device__ __forceinline__ void load(const char *p, double &re, double &im)
-    {
-        double2 v = *(const double2 *)p;
-        re = v.x;
-        im = v.y;
-    }
-    static __device__ __forceinline__ void store(char *p, double re, double im) { *(double2 *)p = make_double2(re, im); }
-};
-template <> struct Cplx<float> {
-    static __device__ __forceinline__ void load(const char *p, double &re, double &im)
-    {
-        float2 v = *(const float2 *)p;
-        re = v.x;
-        im = v.y;
-    }
-    static __device__ __forceinline__ void store(char *p, double re, double im)
-    {
-        *(float2 *)p = make_float2((float)re, (float)im);
-    }
-};
-
 // one wave per axis: lane's k_d and sinc(w_d/2)^deconv_pow along memory-order axis `ax` of the tile (extent ext, from
 // index o there) into kax / sax, and the extreme |k_d| over the tile's index box into ext2 (min, max)
 __device__ __forceinline__ void tile_axis(const PParams &P, const PGeom &g, int ax, int lane, int ext, int64_t o,
@@ -123,19 +102,9 @@ __device__ __forceinline__ void tile_axis(const PParams &P, const PGeom &g, int 
 {
     double k = 0, sp = 1;
     if (lane < ext && g.on[ax]) {
-        const int64_t gi = g.start[ax] + o + lane;
-        double s = (double)gi;
-        if (gi >= g.nmesh[ax] / 2) s -= (double)g.nmesh[ax];
-        const double w = s * g.dw[ax];                  // 2 pi / N first, as pm.py:_block_coords does
-        k = (w * g.nl_n[ax]) / g.boxsize[ax];
-        if (P.deconv_pow) {
-            const double x = 0.5 * w;
-            double sn;
-            if (x < 1e-5 && x > -1e-5) { double x2 = x * x; sn = 1.0 - x2 / 6. + x2 * x2 / 120.; }
-            else sn = sin(x) / x;
-            sp = sn;
-            for (int e = 1; e < P.deconv_pow; e++) sp *= sn;
-        }
+        const double w = mode_w(g.start[ax] + o + lane, g.nmesh[ax], g.dw[ax]);
+        k = k_divided(w, g.nl_n[ax], g.boxsize[ax]);    // as pm.py:_block_coords does
+        if (P.deconv_pow) sp = sinc_pow(w, P.deconv_pow);
     }
     kax[ax * 64 + lane] = k;
     sax[ax * 64 + lane] = sp;
@@ -238,15 +207,8 @@ static int power_setup(const pmx_power *p, int32_t ndim, int32_t elsize, const v
         bx[d] = on ? boxsize[d] : 1.0;
         PMX_REQUIRE(sh[d] >= 0 && nm[d] >= 1, PMX_EINVAL, "bad shape");
     }
-    int ax[3] = {0, 1, 2};
-    auto before = [&](int x, int y) {   // x goes before (slower than) y
-        bool ux = sh[x] == 1, uy = sh[y] == 1;
-        if (ux != uy) return ux;
-        return llabs(sa[x]) > llabs(sa[y]);
-    };
-    for (int i = 0; i < 3; i++)
-        for (int j = i + 1; j < 3; j++)
-            if (before(ax[j], ax[i])) { int t = ax[i]; ax[i] = ax[j]; ax[j] = t; }
+    int32_t ax[3];
+    axis_order(AXES_UNIT_SLOWEST, sh, sa, ax);
     for (int m = 0; m < 3; m++) {
         const int d = ax[m];
         g.ax[m] = d;

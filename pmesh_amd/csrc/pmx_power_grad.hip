@@ -72,9 +72,9 @@ __global__ void __launch_bounds__(PBLOCK) power_vjp_kernel(PParams P, PGeom g, P
         if (lane_on)
             for (int r = r0; r < r1; r++) {
                 const int i0 = r / ext[1], i1 = r - i0 * ext[1];
-                Cplx<T>::store(out.ga + (o[0] + i0) * out.sga[0] + (o[1] + i1) * out.sga[1] + offga2, 0.0, 0.0);
+                CLoad<T>::put(out.ga + (o[0] + i0) * out.sga[0] + (o[1] + i1) * out.sga[1] + offga2, 0.0, 0.0);
                 if (P.cross)
-                    Cplx<T>::store(out.gb + (o[0] + i0) * out.sgb[0] + (o[1] + i1) * out.sgb[1] + offgb2, 0.0, 0.0);
+                    CLoad<T>::put(out.gb + (o[0] + i0) * out.sgb[0] + (o[1] + i1) * out.sgb[1] + offgb2, 0.0, 0.0);
             }
         return;
     }
@@ -108,9 +108,9 @@ __global__ void __launch_bounds__(PBLOCK) power_vjp_kernel(PParams P, PGeom g, P
                 ar[u] = ai[u] = br[u] = bi[u] = 0;
                 if (r < r1 && lane_on) {
                     const int i0 = r / ext[1], i1 = r - i0 * ext[1];
-                    Cplx<T>::load(a + (o[0] + i0) * g.sa[0] + (o[1] + i1) * g.sa[1] + offa2, ar[u], ai[u]);
+                    CLoad<T>::get(a + (o[0] + i0) * g.sa[0] + (o[1] + i1) * g.sa[1] + offa2, ar[u], ai[u]);
                     if (P.cross)
-                        Cplx<T>::load(b + (o[0] + i0) * g.sb[0] + (o[1] + i1) * g.sb[1] + offb2, br[u], bi[u]);
+                        CLoad<T>::get(b + (o[0] + i0) * g.sb[0] + (o[1] + i1) * g.sb[1] + offb2, br[u], bi[u]);
                 }
             }
 #pragma unroll
@@ -193,20 +193,13 @@ __global__ void __launch_bounds__(PBLOCK) power_vjp_kernel(PParams P, PGeom g, P
                 } else if (!(first && !(kmag >= klo && kmag < khi))) {
                     continue;                       // another pass holds the bin of this mode
                 }
-                Cplx<T>::store(out.ga + (o[0] + i0) * out.sga[0] + (o[1] + i1) * out.sga[1] + offga2, gar, gai);
+                CLoad<T>::put(out.ga + (o[0] + i0) * out.sga[0] + (o[1] + i1) * out.sga[1] + offga2, gar, gai);
                 if (P.cross)
-                    Cplx<T>::store(out.gb + (o[0] + i0) * out.sgb[0] + (o[1] + i1) * out.sgb[1] + offgb2, gbr, gbi);
+                    CLoad<T>::put(out.gb + (o[0] + i0) * out.sgb[0] + (o[1] + i1) * out.sgb[1] + offgb2, gbr, gbi);
             }
         }
         __syncthreads();
     }
-}
-
-template <typename T, bool MU, bool POLES>
-static void launch_vjp(dim3 grid, size_t lds, hipStream_t st, const PParams &P, const PGeom &g, const PGrad &o,
-                       const void *a, const void *b, const double *ke, const double *me, const double *coef)
-{
-    power_vjp_kernel<T, MU, POLES><<<grid, PBLOCK, lds, st>>>(P, g, o, (const char *)a, (const char *)b, ke, me, coef);
 }
 
 }  // namespace pmx
@@ -241,17 +234,15 @@ extern "C" int pmx_power_vjp(const pmx_power *p, int32_t ndim, int32_t elsize, c
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)ntiles);
     const bool mu = p->nmu > 0, poles = p->npoles > 0;
-    if (elsize == 8) {
-        if (mu && poles) launch_vjp<double, true, true>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else if (mu) launch_vjp<double, true, false>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else if (poles) launch_vjp<double, false, true>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else launch_vjp<double, false, false>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-    } else {
-        if (mu && poles) launch_vjp<float, true, true>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else if (mu) launch_vjp<float, true, false>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else if (poles) launch_vjp<float, false, true>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-        else launch_vjp<float, false, false>(grid, lds, s, P, g, o, a, b, kedges, muedges, coef);
-    }
+    with_canvas(elsize, [&](auto c) {
+        using T = typename decltype(c)::type;
+        with_bool(mu, [&](auto m) {
+            with_bool(poles, [&](auto pl) {
+                power_vjp_kernel<T, m, pl><<<grid, PBLOCK, lds, s>>>(P, g, o, (const char *)a, (const char *)b, kedges, muedges,
+                                                                    coef);
+            });
+        });
+    });
     PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
