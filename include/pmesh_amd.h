@@ -587,6 +587,37 @@ int pmx_bispec_reduce(int32_t ndim, int32_t elsize, int32_t nb, const void *cons
                       const int64_t *shape, int32_t ntri, const int32_t *triangles, double *acc, double *work,
                       int64_t work_doubles, void *stream);
 
+/* The adjoint of pmx_bispec_reduce with respect to the fields (pmesh_amd.bispectrum.bispectrum_vjp): for every shell
+ * s < nb and every cell x
+ *   outs[s][x] = sum over e in [offsets[s], offsets[s + 1]) of weights[e] * (fields[pairs[2 e]][x] * fields[pairs[2 e + 1]][x]),
+ * products and sums in double, added in list order and rounded once to the element type: the same bits from run to
+ * run.  It replaces one weighted product of two whole fields per entry: every block is read once and every output
+ * written once per call, whatever npairs, with no atomics.  Blocks as in pmx_bispec_reduce: nb real blocks of one
+ * logical shape[0..ndim), one set of byte strides (shared by fields and outs; a padded last axis is a stride, and the
+ * padding is not touched) and elsize 4 or 8.  fields and outs are host arrays of nb device pointers; outs[s] may be
+ * fields[s] (the in-place use: a cell of every field is read before that cell of any output is written), and no
+ * other overlap is allowed.  offsets (nb + 1 int32, non-decreasing, offsets[nb] <= npairs), pairs (npairs x 2 int32)
+ * and weights (npairs float64) are DEVICE arrays; offsets outside [0, npairs] are clamped.  A shell with an empty
+ * range gets zeros: every cell of every output is written.  A pair that names a shell outside [0, nb) contributes
+ * nothing.  Consecutive entries that share pairs[2 e] reuse its value.  nb above PMX_BISPEC_MAX_SHELLS or npairs
+ * above 3 PMX_BISPEC_MAX_TRIANGLES returns PMX_EUNSUPPORTED. */
+int pmx_bispec_pairsum(int32_t ndim, int32_t elsize, int32_t nb, const void *const *fields, void *const *outs,
+                       const int64_t *strides, const int64_t *shape, int32_t npairs, const int32_t *offsets,
+                       const int32_t *pairs, const double *weights, void *stream);
+
+/* The adjoint of pmx_bispec_shells with respect to the field: for every stored mode m of the local complex block
+ *   out[m] = in[shell(m)][m] / prod_d sinc(pi s_d / N_d)^deconv_pow   (divided axis by axis, d = 0, 1, 2)
+ *            0                                                        when m is in no shell,
+ * with |k|, shell(m) and the window computed as in pmx_bispec_shells, so a mode on an edge is in the same shell in
+ * both.  Only the one spectrum a mode belongs to is read; every element of out is written (it may be raw memory) and
+ * out must not be one of the inputs.  Geometry and layouts as in pmx_bispec_shells: in is a host array of nb device
+ * pointers to blocks of one set of byte strides in_strides, kedges a DEVICE array of nb + 1 float64.  nb above
+ * PMX_BISPEC_MAX_SHELLS returns PMX_EUNSUPPORTED. */
+int pmx_bispec_shells_vjp(int32_t ndim, int32_t elsize, int32_t nb, int32_t deconv_pow, const void *const *in,
+                          const int64_t *in_strides, void *out, const int64_t *out_strides, const int64_t *shape,
+                          const int64_t *start, const int64_t *nmesh, const double *boxsize, const double *kedges,
+                          void *stream);
+
 /* ---- initial conditions: tabulated transfers and second-order LPT (the reference's examples/nbody.py:245-282 builds
  * its linear field with a tabulated P(k) through Field.apply; nbody/genic.py:121-166 the 2LPT displacements) --------
  * Geometry as in pmx_apply_transfer: a local block of logical shape[0..ndim) at global index start[], byte strides

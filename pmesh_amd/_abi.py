@@ -194,6 +194,9 @@ DEVICE_ONLY = {
     'bispec_shells': (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _P(_i64), _P(_vp), _P(_i64), _P(_i64), _P(_i64),
                                 _P(_i64), _P(_f64), _vp, _vp]),
     'bispec_reduce': (C.c_int, [_i32, _i32, _i32, _P(_vp), _P(_i64), _P(_i64), _i32, _vp, _vp, _vp, _i64, _vp]),
+    'bispec_pairsum': (C.c_int, [_i32, _i32, _i32, _P(_vp), _P(_vp), _P(_i64), _P(_i64), _i32, _vp, _vp, _vp, _vp]),
+    'bispec_shells_vjp': (C.c_int, [_i32, _i32, _i32, _i32, _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64),
+                                    _P(_i64), _P(_f64), _vp, _vp]),
     'apply_ktable': (C.c_int, [_P(KTable), _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
                                _P(_f64), _vp]),
     'ktable_vjp': (C.c_int, [_P(KTable), _i32, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),

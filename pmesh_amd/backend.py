@@ -284,6 +284,40 @@ class HipBackend(object):
         rows = max(1, min(512, (1 << 23) // max(ntri, 1), (ncells + 127) // 128))
         return rows * ntri
 
+    def bispec_pairsum(self, fields, outs, offsets, pairs, weights):
+        """outs[s] = sum over the entries e of offsets[s] .. offsets[s + 1] of weights[e] * fields[pairs[e][0]] *
+        fields[pairs[e][1]]: real blocks of one shape, dtype and set of strides (outs[s] may be fields[s]), an int32
+        device vector of len(fields) + 1 offsets, an int32 device array (npairs, 2), a float64 device vector
+        (pmx_bispec_pairsum)"""
+        f = fields[0]
+        if f.numel() == 0:
+            return
+        nb = len(fields)
+        if len(outs) != nb or any(o.shape != f.shape or o.stride() != f.stride() or o.dtype != f.dtype
+                                  for o in list(fields) + list(outs)):
+            raise ValueError('bispec_pairsum: the fields and the outputs share one shape, dtype and set of strides')
+        npairs = int(pairs.shape[0])
+        if offsets.numel() != nb + 1 or weights.numel() != npairs or offsets.dtype != torch.int32 or \
+                pairs.dtype != torch.int32 or weights.dtype != torch.float64 or not pairs.is_contiguous():
+            raise ValueError('bispec_pairsum: int32 offsets (nb + 1), int32 pairs (npairs, 2), float64 weights (npairs)')
+        fp = (C.c_void_p * nb)(*[t.data_ptr() for t in fields])
+        op = (C.c_void_p * nb)(*[t.data_ptr() for t in outs])
+        self.call('bispec_pairsum', f.dim(), f.element_size(), nb, fp, op, _byte_strides(f), _abi.i64arr(f.shape, 3),
+                  npairs, offsets.data_ptr(), pairs.data_ptr() if npairs else None,
+                  weights.data_ptr() if npairs else None, self.stream())
+
+    def bispec_shells_vjp(self, ins, out, start, nmesh, boxsize, kedges, deconv_pow=0):
+        """out = the modes of ins[s] in shell s, divided by the window, 0 in no shell: the adjoint of bispec_shells
+        over local complex blocks; the inputs share one shape, dtype and set of strides, `out` may be raw memory
+        (pmx_bispec_shells_vjp)"""
+        if out.numel() == 0:
+            return
+        es = out.element_size()
+        ptrs = (C.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
+        self.call('bispec_shells_vjp', out.dim(), es // 2, len(ins), int(deconv_pow), ptrs, _byte_strides(ins[0]),
+                  out.data_ptr(), _byte_strides(out), _abi.i64arr(out.shape, 3), *_mesh_args(start, nmesh, boxsize),
+                  kedges.data_ptr(), self.stream())
+
     # -- initial conditions: tabulated transfer, 2LPT ----------------------
     def apply_ktable(self, table, v, out, start, nmesh, boxsize):
         """out = T(|k|) v over the local complex block v (pmx_apply_ktable; `table` a _abi.KTable whose x / y are

@@ -31,14 +31,34 @@ amount after the first half is released.  Chunking the shells is not done here.
     r.triangles, r.k, r.B, r.Q, r.counts
     r2 = bispectrum(other_delta_k, r.kedges, deconv_pow=2, counts=r)       # the counts depend on geometry only
 
-Not here: gradients (a ``bispectrum_vjp`` needs an adjoint kernel of its own), cross-bispectra of different fields, a
-line of sight / multipoles, meshes that are not 3-d.
+Gradients.  For L = sum_t v_t B_t put c_t = v_t V^2 / C_t (0 where C_t = 0); the 1 / N of S_t is left out of c_t, it
+cancels against the N of ``c2r_vjp``.  Then
+
+    G_s(x) = sum over t and over every position of s in t of c_t (the product of the other two D at x)
+           = sum_e w_e D_{p_e} D_{q_e}    over the entries e of shell s in a per-target list (``adjoint_pairs``: the bin
+             (i, i, l) gives G_i += 2 c D_i D_l and G_l += c D_i D_i, the bin (i, i, i) gives G_i += 3 c D_i^2),
+    grad(m) = r2c(G_shell(m))(m) / W_m,    0 for modes in no shell,
+
+in the form of ``power_spectrum_vjp``, ``lpt_vjp`` and ``RealField.c2r_vjp`` before ``decompress_vjp``:
+``Re(u.cdot(grad))`` is the derivative of L along u.  Two more kernels (csrc/pmx_bispec_grad.hip): pmx_bispec_pairsum
+reads every shell field once and writes every G_s once, in place, whatever the number of entries, and
+pmx_bispec_shells_vjp gathers the nb spectra r2c(G_s) into the gradient.  ``bispectrum_vjp`` keeps the forward's
+memory: nb buffers next to the input, plus the output.  S is trilinear in the shell fields, so ``bispectrum_jvp`` is
+one pmx_bispec_reduce call over the 2 nb fields [D_0 .., dD_0 ..] with three triples per bin.  Cotangents of ``Q`` and
+``power`` are folded on the host into those of ``B`` and of the shells' P(k), which goes through
+``power_spectrum_vjp``.
+
+    r = bispectrum(delta_k, kedges, deconv_pow=2)
+    g = bispectrum_vjp(delta_k, kedges, v_B=2 * (r.B - target) / sigma2, deconv_pow=2, result=r)   # d chi^2 / d delta_k
+    t = bispectrum_jvp(delta_k, kedges, u_k, deconv_pow=2, result=r)       # t.B, t.Q, t.power: tangents along u_k
+
+Not here: cross-bispectra of different fields, a line of sight / multipoles, meshes that are not 3-d.
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from .power import _complex, _edges, power_spectrum
+from .power import _complex, _edges, _same_layout, power_spectrum, power_spectrum_jvp, power_spectrum_vjp
 
 
 class BispectrumResult(object):
@@ -81,22 +101,61 @@ def alias_bound(pm):
     return float(min(2 * numpy.pi / float(L) * int(n) / 3.0 for L, n in zip(pm.BoxSize, pm.Nmesh)))
 
 
+def _checked(a, kedges, deconv_pow):
+    """the checks the forward and the gradients share: (kedges as float64, the number of shells, triangle_bins)"""
+    pm = a.pm
+    if len(pm.Nmesh) != 3:
+        raise NotImplementedError('bispectra of %d-dimensional meshes: only 3-d meshes' % len(pm.Nmesh))
+    if a.value.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError('bispectrum measures complex64 or complex128 fields')
+    ke = _edges('kedges', kedges)
+    nb = len(ke) - 1
+    if nb > _abi.PMX_BISPEC_MAX_SHELLS:
+        raise ValueError('%d shells: more than PMX_BISPEC_MAX_SHELLS = %d' % (nb, _abi.PMX_BISPEC_MAX_SHELLS))
+    if int(deconv_pow) != deconv_pow or deconv_pow < 0:
+        raise ValueError('deconv_pow must be a non-negative integer')
+    bound = alias_bound(pm)
+    if ke[-1] > bound:
+        raise ValueError('kedges[-1] = %g is past the alias bound min_d (2 pi / BoxSize_d) Nmesh_d / 3 = %g: triangles '
+                         'would close modulo Nmesh' % (ke[-1], bound))
+    return ke, nb, triangle_bins(ke)
+
+
+def _same_bins(name, r, pm, ke, tri):
+    """`r` (the argument `name`) must be the BispectrumResult of this mesh and these edges"""
+    if not isinstance(r, BispectrumResult):
+        raise TypeError('%s must be a BispectrumResult' % name)
+    if r.Nmesh != tuple(int(n) for n in pm.Nmesh) or r.BoxSize != tuple(float(x) for x in pm.BoxSize) \
+            or r.kedges.shape != ke.shape or \
+            not (r.kedges == ke).all() or r.counts.shape != (len(tri),):
+        raise ValueError('%s is not the BispectrumResult of this mesh and these kedges' % name)
+
+
+def _shell_fields(a, kt, nb, deconv_pow, unit):
+    """the nb real fields D_i (unit: I_i) of the spectrum a, each in the buffer of an in-place transform"""
+    from .pm import _blank
+    # (raw memory: the shells entry writes every mode of every block)
+    spectra = [_blank(type(a), a.pm) for _ in range(nb)]
+    backend.get().bispec_shells(a.value, [s.value for s in spectra], a.start, a.pm.Nmesh, a.pm.BoxSize, kt, deconv_pow,
+                                unit)
+    fields = []
+    while spectra:
+        fields.append(spectra.pop(0).c2r(out=Ellipsis))          # each in its own buffer
+    return fields
+
+
+def _real_values(fields):
+    """(of a complex mesh the real part: the transform of a Hermitian spectrum)"""
+    return [f.value.real if f.value.is_complex() else f.value for f in fields]
+
+
 def _shell_sums(a, kt, nb, tri, deconv_pow, unit):
     """sum_x D_i D_j D_l / N per triangle (unit: of the indicator fields), summed over the ranks: a host vector"""
-    from .pm import _blank
     be = backend.get()
     pm = a.pm
-    # (raw memory: the shells entry writes every mode of every block)
-    spectra = [_blank(type(a), pm) for _ in range(nb)]
     acc = torch.zeros(len(tri), dtype=torch.float64, device=be.device)
     try:
-        be.bispec_shells(a.value, [s.value for s in spectra], a.start, pm.Nmesh, pm.BoxSize, kt, deconv_pow, unit)
-        fields = []
-        while spectra:
-            fields.append(spectra.pop(0).c2r(out=Ellipsis))          # each in its own buffer
-        # (of a complex mesh the real part: the transform of a Hermitian spectrum)
-        values = [f.value.real if f.value.is_complex() else f.value for f in fields]
-        be.bispec_reduce(values, tri, acc)
+        be.bispec_reduce(_real_values(_shell_fields(a, kt, nb, deconv_pow, unit)), tri, acc)
     except backend.PmxError as e:
         if e.code == _abi.PMX_EUNSUPPORTED:
             raise ValueError(str(e))
@@ -123,28 +182,9 @@ def bispectrum(field, kedges, deconv_pow=0, counts=None):
     """
     a = _complex(field)
     pm = a.pm
-    if len(pm.Nmesh) != 3:
-        raise NotImplementedError('bispectra of %d-dimensional meshes: only 3-d meshes' % len(pm.Nmesh))
-    if a.value.dtype not in (torch.complex64, torch.complex128):
-        raise ValueError('bispectrum measures complex64 or complex128 fields')
-    ke = _edges('kedges', kedges)
-    nb = len(ke) - 1
-    if nb > _abi.PMX_BISPEC_MAX_SHELLS:
-        raise ValueError('%d shells: more than PMX_BISPEC_MAX_SHELLS = %d' % (nb, _abi.PMX_BISPEC_MAX_SHELLS))
-    if int(deconv_pow) != deconv_pow or deconv_pow < 0:
-        raise ValueError('deconv_pow must be a non-negative integer')
-    bound = alias_bound(pm)
-    if ke[-1] > bound:
-        raise ValueError('kedges[-1] = %g is past the alias bound min_d (2 pi / BoxSize_d) Nmesh_d / 3 = %g: triangles '
-                         'would close modulo Nmesh' % (ke[-1], bound))
-    tri = triangle_bins(ke)
+    ke, nb, tri = _checked(a, kedges, deconv_pow)
     if counts is not None:
-        if not isinstance(counts, BispectrumResult):
-            raise TypeError('counts must be a BispectrumResult')
-        if counts.Nmesh != tuple(int(n) for n in pm.Nmesh) or counts.BoxSize != tuple(float(x) for x in pm.BoxSize) \
-                or counts.kedges.shape != ke.shape or \
-                not (counts.kedges == ke).all() or counts.counts.shape != (len(tri),):
-            raise ValueError('counts is not the BispectrumResult of this mesh and these kedges')
+        _same_bins('counts', counts, pm, ke, tri)
 
     be = backend.get()
     kt = torch.from_numpy(ke).to(be.device)
@@ -157,3 +197,188 @@ def bispectrum(field, kedges, deconv_pow=0, counts=None):
     # P of a / W: power_spectrum divides the product a conj(a), so its exponent is twice the amplitude's
     pk = power_spectrum(a, ke, deconv_pow=2 * int(deconv_pow))
     return BispectrumResult(ke, tri.astype('i8'), sums, cnt, pk, pm.BoxSize, pm.Nmesh)
+
+
+# ---- gradients -----------------------------------------------------------------------------------------------------
+
+def _spectrum_only(field):
+    from .pm import RealField, BaseComplexField
+    if isinstance(field, RealField):
+        raise TypeError('the gradients of bispectrum take ComplexField objects: transform the RealField with r2c and '
+                        'back-propagate through it with r2c_vjp')
+    if not isinstance(field, BaseComplexField):
+        raise TypeError('bispectrum measures RealField or ComplexField objects, not %s' % type(field).__name__)
+    return field
+
+
+def adjoint_pairs(triangles, coef, nb):
+    """The per-target list of the adjoint of the triangle sums: for L = sum_t coef_t sum_x D_i D_j D_l over the bins
+    t = (i, j, l) of `triangles`, dL / dD_s(x) = sum_e weights[e] D_p(x) D_q(x) over the entries
+    e in [offsets[s], offsets[s + 1]) with (p, q) = pairs[e], p <= q.
+
+    One merged entry per (triangle, distinct target): weight coef, 2 coef or 3 coef for a shell that the bin names
+    once, twice or three times.  Sorted by target, then p, then q (pmx_bispec_pairsum keeps D_p while consecutive
+    entries share p).  Bins whose coef is 0 or not finite are dropped.  Returns (offsets int32 (nb + 1), pairs int32
+    (npairs, 2), weights float64 (npairs))."""
+    tri = numpy.asarray(triangles).astype('i8').reshape(-1, 3)
+    c = numpy.asarray(coef, dtype='f8').reshape(-1)
+    if len(c) != len(tri):
+        raise ValueError('adjoint_pairs: %d coefficients for %d triangles' % (len(c), len(tri)))
+    if len(tri) and (tri.min() < 0 or tri.max() >= nb):
+        raise ValueError('adjoint_pairs: a triangle names a shell outside [0, %d)' % nb)
+    keep = numpy.isfinite(c) & (c != 0)
+    tri, c = tri[keep], c[keep]
+    tgt, pq, w = [], [], []
+    for pos in range(3):
+        s = tri[:, pos]
+        first = numpy.ones(len(tri), dtype=bool)
+        for before in range(pos):
+            first &= tri[:, before] != s                     # an earlier position has made this target's entry
+        rest = tri[:, [x for x in range(3) if x != pos]]
+        tgt.append(s[first])
+        pq.append(numpy.sort(rest[first], axis=1))
+        w.append(((tri == s[:, None]).sum(axis=1) * c)[first])
+    tgt, pq, w = numpy.concatenate(tgt), numpy.concatenate(pq), numpy.concatenate(w)
+    order = numpy.lexsort((pq[:, 1], pq[:, 0], tgt))
+    offsets = numpy.concatenate([[0], numpy.cumsum(numpy.bincount(tgt, minlength=nb))])
+    return offsets.astype('i4'), numpy.ascontiguousarray(pq[order]).astype('i4'), w[order]
+
+
+def _cotangent(name, v, n):
+    """a cotangent as n float64 values (None: zeros)"""
+    if v is None:
+        return numpy.zeros(n)
+    v = numpy.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+    if v.shape != (n,):
+        raise ValueError('%s must have the %d values of its column, not the shape %s' % (name, n, v.shape))
+    return v.astype('f8')
+
+
+def _denominator(p, tri):
+    """den_t = P_i P_j + P_j P_l + P_l P_i of Q and its formal partial derivatives by P_i, P_j, P_l, (3, ntri)"""
+    i, j, l = tri.T
+    return p[i] * p[j] + p[j] * p[l] + p[l] * p[i], numpy.stack([p[j] + p[l], p[i] + p[l], p[i] + p[j]])
+
+
+def bispectrum_vjp(field, kedges, v_B=None, v_Q=None, v_power=None, deconv_pow=0, result=None):
+    """The gradient of L = sum_t v_B[t] B_t + sum_t v_Q[t] Q_t + sum_s v_power[s] power_s of
+    ``bispectrum(field, kedges, deconv_pow)`` with respect to the field: see the module docstring.
+
+    field : ComplexField as for bispectrum (a RealField raises TypeError: go through r2c_vjp).
+    v_B, v_Q : ntri real values, v_power : nb real values; None counts as zero, and empty bins (NaN in the forward)
+        contribute nothing.  ``k``, ``counts`` and ``ntriangles`` are piecewise constant and have no gradient.  v_Q and
+        v_power are folded on the host: with den = P_i P_j + P_j P_l + P_l P_i, v_B += v_Q / den and
+        v_power[s] -= sum_t v_Q[t] B_t / den_t^2 d den_t / d P_s; the power part goes through
+        power_spectrum_vjp(field, kedges, v_power=..., deconv_pow=2 * deconv_pow).
+    result : the BispectrumResult of the same arguments, for its counts, B and power; without it one forward call is
+        made.
+
+    Returns a field of the input's type in the form of power_spectrum_vjp, lpt_vjp and RealField.c2r_vjp before
+    decompress_vjp: ``Re(u.cdot(grad))`` is the derivative of L along u.  Memory: the forward's nb buffers next to the
+    input, plus the output.  On several ranks every step is local or a distributed transform.
+    """
+    from .lpt import _spectrum_of
+    from .pm import _blank
+    a = _spectrum_only(field)
+    pm = a.pm
+    ke, nb, tri = _checked(a, kedges, deconv_pow)
+    ntri = len(tri)
+    vb, vq, vp = _cotangent('v_B', v_B, ntri), _cotangent('v_Q', v_Q, ntri), _cotangent('v_power', v_power, nb)
+    if result is None:
+        result = bispectrum(a, ke, deconv_pow=deconv_pow)
+    else:
+        _same_bins('result', result, pm, ke, tri)
+
+    # Q and power folded into the cotangents of B and of the shells' P(k)
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        vb = numpy.where(numpy.isfinite(result.B), vb, 0.0)
+        vp = numpy.where(numpy.isfinite(result.power), vp, 0.0)
+        if v_Q is not None:
+            den, dden = _denominator(result.power, tri)
+            ok = numpy.isfinite(result.Q) & (vq != 0)
+            vb = vb + numpy.where(ok, vq / den, 0.0)
+            back = numpy.where(ok, vq * result.B / den ** 2, 0.0)
+            for pos in range(3):
+                numpy.subtract.at(vp, tri[:, pos], numpy.where(ok, back * dden[pos], 0.0))
+        volume = float(numpy.prod(result.BoxSize))
+        coef = numpy.where(result.counts > 0, vb * volume ** 2 / result.counts, 0.0)
+    offsets, pairs, weights = adjoint_pairs(tri, coef, nb)
+
+    be = backend.get()
+    grad = None
+    if len(weights):
+        kt = torch.from_numpy(ke).to(be.device)
+        try:
+            fields = _shell_fields(a, kt, nb, int(deconv_pow), False)
+            for f in fields:
+                if f.value.is_complex():
+                    f.value.imag.zero_()                     # a complex mesh: the real part is what the forward measures
+            values = _real_values(fields)
+            be.bispec_pairsum(values, values, torch.from_numpy(offsets).to(be.device),
+                              torch.from_numpy(pairs).to(be.device), torch.from_numpy(weights).to(be.device))
+            del values
+            spectra = []
+            while fields:
+                spectra.append(_spectrum_of(fields.pop(0), a))   # r2c(G_s), each in its own buffer
+            # (the kernel writes every mode of the block: only the GPU backend hands out raw memory)
+            grad = _blank(type(a), pm) if be.name == 'hip' and a.value.numel() else pm.create(type=type(a))
+            be.bispec_shells_vjp([s.value for s in spectra], grad.value, a.start, pm.Nmesh, pm.BoxSize, kt,
+                                 int(deconv_pow))
+        except backend.PmxError as e:
+            if e.code == _abi.PMX_EUNSUPPORTED:
+                raise ValueError(str(e))
+            raise
+    if vp.any():
+        gp = power_spectrum_vjp(a, ke, v_power=vp, deconv_pow=2 * int(deconv_pow))
+        if grad is None:
+            grad = gp
+        else:
+            grad.value[...] += gp.value
+    if grad is None:
+        grad = pm.create(type=type(a))
+    return grad
+
+
+def bispectrum_jvp(field, kedges, v_field, deconv_pow=0, result=None):
+    """The tangent of bispectrum along v_field: a BispectrumResult whose ``sums``, ``B``, ``Q`` and ``power`` are
+    tangents and whose ``counts``, ``ntriangles``, ``k`` and ``triangles`` are the forward's.
+
+    S is trilinear in the shell fields, so its tangent is the sum of the three triples (dD_i, D_j, D_l), (D_i, dD_j,
+    D_l), (D_i, D_j, dD_l) per bin: one pmx_bispec_reduce call over the 2 nb fields [D_0 .., dD_0 ..], which needs
+    2 nb <= PMX_BISPEC_MAX_SHELLS.  ``power`` comes from power_spectrum_jvp, dQ = dB / den - B d den / den^2.
+    v_field : a ComplexField of the field's layout.  result : as for bispectrum_vjp."""
+    a = _spectrum_only(field)
+    v = _spectrum_only(v_field)
+    pm = a.pm
+    ke, nb, tri = _checked(a, kedges, deconv_pow)
+    if 2 * nb > _abi.PMX_BISPEC_MAX_SHELLS:
+        raise ValueError('%d shells: bispectrum_jvp sums over the 2 nb fields [D, dD] and takes at most '
+                         'PMX_BISPEC_MAX_SHELLS / 2 = %d shells' % (nb, _abi.PMX_BISPEC_MAX_SHELLS // 2))
+    _same_layout(a, v)
+    if result is None:
+        result = bispectrum(a, ke, deconv_pow=deconv_pow)
+    else:
+        _same_bins('result', result, pm, ke, tri)
+    ntri = len(tri)
+    triples = numpy.concatenate([tri + nb * numpy.eye(3, dtype='i4')[pos] for pos in range(3)]).astype('i4')
+
+    be = backend.get()
+    kt = torch.from_numpy(ke).to(be.device)
+    acc = torch.zeros(3 * ntri, dtype=torch.float64, device=be.device)
+    try:
+        fields = _shell_fields(a, kt, nb, int(deconv_pow), False) + _shell_fields(v, kt, nb, int(deconv_pow), False)
+        be.bispec_reduce(_real_values(fields), torch.from_numpy(triples).to(be.device), acc)
+        del fields
+    except backend.PmxError as e:
+        if e.code == _abi.PMX_EUNSUPPORTED:
+            raise ValueError(str(e))
+        raise
+    if pm.comm.size > 1:
+        acc = pm.comm.allreduce(acc)
+    dsums = acc.cpu().numpy().reshape(3, ntri).sum(axis=0) / float(numpy.prod([int(n) for n in pm.Nmesh]))
+    dpk = power_spectrum_jvp(a, ke, v_field=v, deconv_pow=2 * int(deconv_pow))
+    t = BispectrumResult(ke, tri.astype('i8'), dsums, result.counts, dpk, pm.BoxSize, pm.Nmesh)
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        den, dden = _denominator(result.power, tri)
+        t.Q = t.B / den - result.B * (dden * t.power[tri.T]).sum(axis=0) / den ** 2
+    return t

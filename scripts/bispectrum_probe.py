@@ -20,6 +20,15 @@ in f8 and f4, prints one JSON line per case:
                                    parity case the error of the composition out of the complex64 c2r of masked copies
                                    and torch products in float64 against the numpy-f8 estimator, in units of
                                    sum_x |D_i D_j D_l| / N, next to that of bispectrum() itself
+    python scripts/bispectrum_probe.py --vjp [--mesh 256 512] [--dtype f8 f4]   the stages of bispectrum_vjp
+                                   (csrc/pmx_bispec_grad.hip), one JSON line per case: shells_ms, c2r_ms, pairsum_ms (all
+                                   entries of adjoint_pairs, in place), r2c_ms (the nb in-place r2c), shells_vjp_ms, next
+                                   to reduce_ms of the forward on the same fields; vjp_ms (bispectrum_vjp with result=)
+                                   next to forward_half_ms (shells + c2r + reduce, the sums half of bispectrum); then the
+                                   yardstick of the f4 tolerance of tests/test_bispectrum_gradients.py: per parity case
+                                   the error of the gradient composed from bispec_shells, the complex64 c2r, torch
+                                   products in float64, the complex64 r2c and torch.where against the numpy-f8
+                                   gradient, relative to its largest modulus, next to that of bispectrum_vjp itself
 Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/bispectrum_probe.py --no-torch ...`
 (a run of its own).
 """
@@ -35,7 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from pmesh_amd import backend  # noqa: E402
-from pmesh_amd.bispectrum import bispectrum, triangle_bins  # noqa: E402
+from pmesh_amd.bispectrum import adjoint_pairs, bispectrum, bispectrum_vjp, triangle_bins  # noqa: E402
 from pmesh_amd.pm import ParticleMesh, _blank  # noqa: E402
 
 HBM_RATE = 6.29e12
@@ -74,6 +83,95 @@ def f4_error():
     print('largest composition error / scale: %.4g' % worst)
 
 
+def f4_vjp_error():
+    from tests import test_bispectrum as T
+    from tests import test_bispectrum_gradients as G
+    worst = 0
+    for Nmesh, BoxSize in T.PARITY_MESHES:
+        for kind in ('T', 'U', 'c2c'):
+            for dp in (0, 2):
+                e = G.composition_error(kind, Nmesh, BoxSize, dp)
+                c, ke, r, v, coef = G.parity_case(kind, Nmesh, BoxSize, dp, 'f4')
+                want, _, _ = G.reference(c, ke, dp, coef)
+                got = bispectrum_vjp(c, ke, v_B=v, deconv_pow=dp, result=r).value.cpu().numpy()
+                mine = float(numpy.abs(got - want).max() / numpy.abs(want).max())
+                worst = max(worst, e)
+                print('composition f4 gradient error / max |grad|: %s %s deconv %d: %.4g   (bispectrum_vjp(): %.4g)'
+                      % (Nmesh, kind, dp, e, mine), flush=True)
+    print('largest composition gradient error / max |grad|: %.4g' % worst)
+
+
+def vjp_stages(N, dt, nb, reps):
+    """the stages of bispectrum_vjp on an N^3 mesh, each timed on the buffers the stage before left"""
+    from pmesh_amd.lpt import _spectrum_of
+    be = backend.get()
+    pm = ParticleMesh([N, N, N], BoxSize=1000., dtype=dt)
+    c = pm.create(type='complex')
+    g = torch.Generator(device=c.value.device).manual_seed(1)
+    x = pm.create(type='real')
+    x.value.copy_(torch.randn(x.value.shape, generator=g, device=x.value.device, dtype=x.value.dtype))
+    x.r2c(out=c)
+    del x
+    kf = 2 * numpy.pi / 1000.
+    ke = kf * numpy.linspace(1, N / 3.0, nb + 1)
+    tri = triangle_bins(ke)
+    kt = torch.from_numpy(ke).to(be.device)
+    tt = torch.from_numpy(tri).to(be.device)
+    offsets, pairs, weights = adjoint_pairs(tri, numpy.random.RandomState(1).normal(size=len(tri)), nb)
+    ot, pt, wt = (torch.from_numpy(a).to(be.device) for a in (offsets, pairs, weights))
+    spectra = [_blank(type(c), pm) for _ in range(nb)]
+
+    def shells():
+        be.bispec_shells(c.value, [s.value for s in spectra], c.start, pm.Nmesh, pm.BoxSize, kt, 0, False)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    t_shells = timed(shells, reps)
+    # (the transforms are in place: the whole chain again for each timed round)
+    t_c2r, t_pair, t_r2c = [], [], []
+    for _ in range(reps + 1):
+        shells()
+        t, fields = event_timed(lambda: [s.c2r(out=Ellipsis) for s in spectra])
+        t_c2r.append(t)
+        values = [f.value for f in fields]
+        t, _ = event_timed(lambda: be.bispec_pairsum(values, values, ot, pt, wt))
+        t_pair.append(t)
+        t, back = event_timed(lambda: [_spectrum_of(f, c) for f in fields])
+        t_r2c.append(t)
+    out = _blank(type(c), pm)
+    t_gather = timed(lambda: be.bispec_shells_vjp([s.value for s in back], out.value, c.start, pm.Nmesh, pm.BoxSize, kt,
+                                                  0), reps)
+    # the forward's reduction on the same run: shell fields again
+    shells()
+    values = [s.c2r(out=Ellipsis).value for s in spectra]
+    acc = torch.zeros(len(tri), dtype=torch.float64, device=be.device)
+    work = torch.empty(be.bispec_work(len(tri), values[0].numel()), dtype=torch.float64, device=be.device)
+
+    def reduce():
+        acc.zero_()
+        be.bispec_reduce(values, tt, acc, work=work)
+    t_reduce = timed(reduce, reps)
+    del spectra, fields, values, back, out
+    torch.cuda.empty_cache()
+    r = bispectrum(c, ke)
+    v = numpy.random.RandomState(2).normal(size=len(tri))
+    t_vjp = timed(lambda: bispectrum_vjp(c, ke, v_B=v, result=r), reps)
+    med = lambda ts: float(numpy.median(ts[1:]))            # noqa: E731
+    rec = {'mesh': N, 'dtype': dt, 'shells': nb, 'ntri': len(tri), 'npairs': len(weights),
+           'shells_ms': round(t_shells, 3), 'c2r_ms': round(med(t_c2r), 3), 'pairsum_ms': round(med(t_pair), 3),
+           'r2c_ms': round(med(t_r2c), 3), 'shells_vjp_ms': round(t_gather, 3), 'reduce_ms': round(t_reduce, 3),
+           'vjp_ms': round(t_vjp, 3), 'forward_half_ms': round(t_shells + med(t_c2r) + t_reduce, 3)}
+    print(json.dumps(rec), flush=True)
+    del c, pm
+    torch.cuda.empty_cache()
+
+
 def ntri_sweep(N, nb, reps):
     be = backend.get()
     fields = [torch.randn((N, N, N + 2), device=be.device, dtype=torch.float64)[..., :N] for _ in range(nb)]
@@ -95,11 +193,17 @@ def main():
     ap.add_argument('--no-torch', action='store_true')
     ap.add_argument('--ntri-sweep', action='store_true')
     ap.add_argument('--f4-error', action='store_true')
+    ap.add_argument('--vjp', action='store_true')
     args = ap.parse_args()
     be = backend.get()
     nb = args.shells
     if args.f4_error:
         return f4_error()
+    if args.vjp:
+        for N in args.mesh:
+            for dt in args.dtype:
+                vjp_stages(N, dt, nb, args.reps)
+        return f4_vjp_error()
     if args.ntri_sweep:
         for N in args.mesh:
             ntri_sweep(N, nb, args.reps)
