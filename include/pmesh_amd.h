@@ -729,6 +729,43 @@ int pmx_lpt2_source_jvp(int32_t ndim, int32_t elsize, const void *const *in, con
                         const void *const *tangent, const int64_t *tangent_strides, void *out,
                         const int64_t *out_strides, const int64_t *shape, double scale, void *stream);
 
+/* ---- survey power multipoles with a local line of sight (the FFT form of the Yamamoto estimator: Bianchi et al. 2015,
+ * Scoccimarro 2015, Hand et al. 2017; what nbodykit's ConvolvedFFTPower computes; pmesh_amd.survey) -------------------
+ * Geometry as in pmx_apply_transfer, 3-d blocks only.  Definitions:
+ *   Cell position.  Cell g (global index, 0 <= g_d < N_d) sits at x_d = (g_d * L_d) / N_d, in double and in this order
+ *     of operations: the position paint assigns to that cell, not wrapped to negative values.
+ *   Direction.  origin is the observer, in the box coordinates of particle positions; r = x - origin is never wrapped
+ *     periodically; r_hat = r / |r|.
+ *   Real orthonormal harmonics Y_lm without the Condon-Shortley phase.  With
+ *     N_lm = sqrt((2l+1) / (4 pi) (l-|m|)! / (l+|m|)!) and P_l^m(c) = (1 - c^2)^(m/2) d^m P_l / dc^m,
+ *       m = 0:  N_l0 P_l(cos th)
+ *       m > 0:  sqrt2 N_lm P_l^m(cos th) cos(m ph)
+ *       m < 0:  sqrt2 N_l|m| P_l^|m|(cos th) sin(|m| ph)
+ *     for a unit vector (x, y, z) with cos th = z, ph = atan2(y, x): Y_22 is proportional to +(x^2 - y^2), Y_21 to +xz,
+ *     Y_2,-1 to +yz.  For a zero vector (r = 0 or k = 0), Y_00 = 1 / sqrt(4 pi) and every Y_lm with l > 0 is 0.
+ *   The multipole field.  With r2c in the package's convention (divided by prod N, phase exp(-i k.x)),
+ *       A_l(k) = (4 pi / (2l+1)) sum_m Y_lm(k_hat) * r2c[F * Y_lm(r_hat)](k)
+ *     which by the addition theorem is (1 / prod N) sum_x F(x) L_l(k_hat . r_hat) exp(-i k.x), L_l the Legendre
+ *     polynomial, taken as [l == 0] at k = 0 or r = 0; A_0 = r2c[F].
+ *   The result.  P_l(bin) = (2l+1) V <A_0 conj(A_l)> with the bins, counts, Hermitian weighting and rank sum of
+ *     pmx_power_project.  Even orders only: for odd l, A_l is anti-Hermitian and the mirrored-mode rule does not hold.
+ * Both entries evaluate Y_lm as a Cartesian polynomial of the unit vector (no trigonometric calls, one sqrt and one
+ * division per element), compute in double and round once on the store, take any axis order (C, transposed, padded,
+ * strided) and elsize 4 or 8 per (real) component, and return PMX_EUNSUPPORTED for ndim != 3, ell not in {0, 2, 4} or
+ * |m| > ell. */
+
+/* Real blocks: out = in * Y_lm(r_hat) with r_hat the direction from origin[0..3) to the cell.  out may alias in (same
+ * strides); every element of out is written, so out may be raw memory. */
+int pmx_ylm_weight(int32_t ell, int32_t m, int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides,
+                   void *out, const int64_t *out_strides, const int64_t *shape, const int64_t *start,
+                   const int64_t *nmesh, const double *boxsize, const double *origin, void *stream);
+
+/* Complex blocks: acc = beta * acc + (4 pi / (2l+1)) Y_lm(k_hat) * in, beta 0 or 1; with beta = 0 acc is not read and
+ * may be raw memory.  k as in pmx_apply_transfer; only its direction matters. */
+int pmx_ylm_accumulate(int32_t ell, int32_t m, int32_t beta, int32_t ndim, int32_t elsize, const void *in,
+                       const int64_t *in_strides, void *acc, const int64_t *acc_strides, const int64_t *shape,
+                       const int64_t *start, const int64_t *nmesh, const double *boxsize, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -212,6 +212,10 @@ DEVICE_ONLY = {
                                   _vp]),
     'lpt2_source_jvp': (C.c_int, [_i32, _i32, _P(_vp), _P(_i64), _P(_vp), _P(_i64), _vp, _P(_i64), _P(_i64), _f64,
                                   _vp]),
+    'ylm_weight': (C.c_int, [_i32, _i32, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_f64),
+                             _P(_f64), _vp]),
+    'ylm_accumulate': (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _P(_i64), _vp, _P(_i64), _P(_i64), _P(_i64), _P(_i64),
+                                 _P(_f64), _vp]),
 }
 
 

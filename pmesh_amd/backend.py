@@ -343,6 +343,26 @@ class HipBackend(object):
                   _byte_strides(v), out.data_ptr(), _byte_strides(out), _abi.i64arr(v.shape, 3),
                   *_mesh_args(start, nmesh, boxsize), self.stream())
 
+    # -- survey multipoles: the harmonic passes ------------------------------
+    def ylm_weight(self, ell, m, v, out, start, nmesh, boxsize, origin):
+        """out = v * Y_lm(r_hat) over the local real block v, r_hat the direction from `origin` to each cell
+        (pmx_ylm_weight); out may be v or raw memory"""
+        if v.numel() == 0:
+            return
+        self.call('ylm_weight', int(ell), int(m), v.dim(), v.element_size(), v.data_ptr(), _byte_strides(v),
+                  out.data_ptr(), _byte_strides(out), _abi.i64arr(v.shape, 3), *_mesh_args(start, nmesh, boxsize),
+                  _abi.f64arr(origin, 3), self.stream())
+
+    def ylm_accumulate(self, ell, m, beta, v, acc, start, nmesh, boxsize):
+        """acc = beta * acc + (4 pi / (2 ell + 1)) Y_lm(k_hat) v over the local complex block v, beta 0 or 1
+        (pmx_ylm_accumulate); with beta = 0 acc may be raw memory"""
+        if v.numel() == 0:
+            return
+        es = v.element_size()
+        self.call('ylm_accumulate', int(ell), int(m), int(beta), v.dim(), es // 2, v.data_ptr(), _byte_strides(v),
+                  acc.data_ptr(), _byte_strides(acc), _abi.i64arr(v.shape, 3), *_mesh_args(start, nmesh, boxsize),
+                  self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""
