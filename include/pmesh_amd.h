@@ -766,6 +766,22 @@ int pmx_ylm_accumulate(int32_t ell, int32_t m, int32_t beta, int32_t ndim, int32
                        const int64_t *in_strides, void *acc, const int64_t *acc_strides, const int64_t *shape,
                        const int64_t *start, const int64_t *nmesh, const double *boxsize, void *stream);
 
+/* ---- interlaced painting: the combine pass (Hockney & Eastwood; Sefusatti et al. 2016; what nbodykit's
+ * interlaced=True computes; pmesh_amd.interlace) ----------------------------------------------------------------------
+ * For every mode of a strided block of a spectrum (global index g_d = idx_d + start_d, ndim 1 to 3):
+ *     acc = (a * acc + b * exp(i * theta) * in) / prod_d sinc(w_d / 2)^deconv_pow,    theta = sum_d shift_d * w_d
+ * with the circular frequency w_d = 2 pi / N_d * (g_d - N_d [g_d >= N_d / 2]) (the Nyquist frequency negative, pmesh's
+ * convention and the one nbodykit's interlacing uses) and `shift` in cells, any real numbers: exp(i theta) undoes the
+ * displacement of a mesh painted with the transform shifted by `shift`.  deconv_pow >= 0, 0: no division.  With a == 0
+ * acc is not read and may be raw memory.  elsize 4 or 8 per (real) component of complex f4 / f8 storage; the
+ * arithmetic is in double, rounded once on the store.  The phase is formed from the signed mode numbers,
+ * theta / pi = sum_d 2 shift_d m_d / N_d reduced term by term, so it is as accurate at |m| = 2^16 as at m = 1.  `in`
+ * and `acc` take any axis order (C, transposed, padded, strided), each its own; the byte ranges they reach must not
+ * overlap (PMX_EINVAL).  PMX_EUNSUPPORTED for a plane of 2^31 modes or more. */
+int pmx_phase_combine(int32_t ndim, int32_t elsize, const void *in, const int64_t *in_strides, void *acc,
+                      const int64_t *acc_strides, const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                      const double *shift, double a, double b, int32_t deconv_pow, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -8,6 +8,7 @@
     from pmesh_amd.bispectrum import bispectrum    # binned B(k1, k2, k3) over closed triangle bins, counts, Q
     from pmesh_amd.bispectrum import bispectrum_vjp, bispectrum_jvp   # and its gradients
     from pmesh_amd.survey import survey_multipoles, multipole_field   # P_0,2,4 with a local line of sight (Yamamoto)
+    from pmesh_amd.interlace import paint_interlaced, interlaced_field   # alias-cancelling spectra (interlacing)
     from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
     from pmesh_amd.lpt import lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp   # and their gradients
 

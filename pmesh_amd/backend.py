@@ -363,6 +363,17 @@ class HipBackend(object):
                   acc.data_ptr(), _byte_strides(acc), _abi.i64arr(v.shape, 3), *_mesh_args(start, nmesh, boxsize),
                   self.stream())
 
+    # -- interlaced painting: the combine pass ---------------------------------
+    def phase_combine(self, v, acc, start, nmesh, shift, a, b, deconv_pow=0):
+        """acc = (a * acc + b * exp(i sum_d shift_d w_d) * v) / prod_d sinc(w_d / 2)^deconv_pow over the local complex
+        block v (pmx_phase_combine); v and acc must not overlap, and with a = 0 acc may be raw memory"""
+        if v.numel() == 0:
+            return
+        es = v.element_size()
+        self.call('phase_combine', v.dim(), es // 2, v.data_ptr(), _byte_strides(v), acc.data_ptr(),
+                  _byte_strides(acc), _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3),
+                  _abi.f64arr(shift, 3), float(a), float(b), int(deconv_pow), self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""

@@ -46,8 +46,8 @@ well.
     r = survey_multipoles(F, kedges, origin=[-1500., 0., 0.], poles=(0, 2, 4), deconv_pow=2)
     r.k, r.modes, r.poles[2], r.A0
 
-Not here: gradients, odd orders, interlacing, and the FKP normalisation and shot-noise terms (sums over catalogue
-columns: the caller computes them and scales the result).
+Not here: gradients, odd orders, and the FKP normalisation and shot-noise terms (sums over catalogue columns: the
+caller computes them and scales the result).  An interlaced field comes from ``pmesh_amd.interlace.interlaced_field``.
 """
 import numpy
 
