@@ -782,6 +782,61 @@ int pmx_phase_combine(int32_t ndim, int32_t elsize, const void *in, const int64_
                       const int64_t *acc_strides, const int64_t *shape, const int64_t *start, const int64_t *nmesh,
                       const double *shift, double a, double b, int32_t deconv_pow, void *stream);
 
+/* ---- binned correlation function (what nbodykit's FFTCorr computes: a conj(b) transformed back and binned by
+ * RealField.x; pmesh_amd.correlation) -----------------------------------------------------------------------------------
+ * Definition, for a 1-, 2- or 3-d real mesh (f4 or f8) with the spectra a and b (b = a: the auto correlation):
+ *   1. S = a conj(b) / prod_d sinc(w_d / 2)^deconv_pow                                  (pmx_spectral_product)
+ *   2. xi = c2r(S): with pmesh's normalisation xi(x) is the mean over y of A(y + x) B(y).  The k = 0 mode is kept;
+ *      removing the mean is the caller's business.
+ *   3. per cell, in double: r_d = (s_d * L_d) / N_d with the signed index s_d (global index i_d, minus N_d when
+ *      i_d >= N_d / 2) — what RealField.x of an f8 mesh holds, with the same two roundings —
+ *      |r| = sqrt((r_0^2 + r_1^2) + r_2^2),   mu = ((r_0 los_0 + r_1 los_1) + r_2 los_2) / |r| (0 at r = 0).
+ *   4. a cell is in r bin j when redges[j] <= |r| < redges[j + 1] (dropped otherwise), in mu bin m when
+ *      muedges[m] <= mu < muedges[m + 1], the last bin closed on the right.  Every cell has weight 1: there is no
+ *      Hermitian doubling on the real side.
+ *   5. the raw sums below are added over the ranks first, then divided: xi_l(r) = (2l + 1) sum x L_l(mu) / count.
+ *
+ * pmx_corr_project adds the sums of the local real block x (steps 3 to 5; any real mesh, not only a xi) into `acc`, a
+ * zeroed DEVICE array of float64.  p: nk is the number of r bins, nmu, npoles, poles, los as in pmx_power_project,
+ * volume multiplies every value, hermitian and deconv_pow must be 0 (PMX_EINVAL); the PMX_POWER_MAX_* limits apply
+ * (PMX_EUNSUPPORTED).  elsize 4 or 8: one real element, loaded as such and widened to double.  Any byte strides: C
+ * order, the padded last axis of an in-place transform, transposed views, a block at `start` inside a larger mesh.
+ * redges (nk + 1) and muedges (nmu + 1, or NULL) are DEVICE arrays of float64.
+ * Layout of acc (S = 3 + npoles doubles per r bin, then 4 per (r, mu) cell):
+ *   acc[j*S + 0] count    acc[j*S + 1] sum |r|    acc[j*S + 2] sum x    acc[j*S + 3 + p] sum x L_ell_p(mu)
+ *   acc[nk*S + (j*nmu + m)*4 + {0, 1, 2, 3}]   count, sum |r|, sum mu, sum x
+ * One read of the block, nothing mesh-sized written: one workgroup per 16 x 16 x 64 tile in memory order keeps the
+ * window of r bins its index box can reach in LDS (|r| is monotone in each |r_d|; a tile may straddle N / 2), sums
+ * runs of cells of one bin in registers, and adds the window to acc once per tile and touched bin (float atomics: the
+ * last bits may differ from run to run). */
+int pmx_corr_project(const pmx_power *p, int32_t ndim, int32_t elsize, const void *x, const int64_t *x_strides,
+                     const int64_t *shape, const int64_t *start, const int64_t *nmesh, const double *boxsize,
+                     const double *redges, const double *muedges, double *acc, void *stream);
+
+/* The adjoint of pmx_corr_project with respect to the mesh: writes every cell of the real block g (its own byte
+ * strides; raw memory is allowed) with
+ *   volume * (c1[j] + sum_p cp[p][j] L_ell_p(mu) + c2[j, mubin(mu)])      (the last term 0 when mu is outside muedges)
+ * for the cell's r bin j, and 0 for a cell outside redges.  coef is a DEVICE array of float64 in the layout of acc
+ * without the count, |r| and mu columns (C = 1 + npoles doubles per r bin, then 1 per (r, mu) cell):
+ *   coef[j*C + 0] c1[j]     coef[j*C + 1 + p] cp[p][j]     coef[nk*C + j*nmu + m] c2[j, m]
+ * The tiles, windows and bin search are those of pmx_corr_project, so every cell reads the bin the forward put it in.
+ * No atomics; the result is deterministic. */
+int pmx_corr_vjp(const pmx_power *p, int32_t ndim, int32_t elsize, void *g, const int64_t *g_strides,
+                 const int64_t *shape, const int64_t *start, const int64_t *nmesh, const double *boxsize,
+                 const double *redges, const double *muedges, const double *coef, void *stream);
+
+/* out = [out +] scale * x * (conj_y ? conj(y) : y) / prod_d sinc(w_d / 2)^deconv_pow over a strided block of a
+ * spectrum (w_d as in pmx_phase_combine; ndim 1 to 3; elsize 4 or 8 per component; the arithmetic in double, rounded
+ * once on the store): the product of step 1 above and both products of its gradient, one streaming kernel with two
+ * reads and one write per mode (three reads when accumulating).  x, y and out take any axis order, each its own
+ * strides; out may be exactly x or exactly y (same pointer and strides), and x may be y; any other overlap of out with
+ * an input is refused (PMX_EINVAL).  Without `accumulate` out is not read and may be raw memory.  PMX_EUNSUPPORTED for
+ * a plane of 2^31 modes or more. */
+int pmx_spectral_product(int32_t ndim, int32_t elsize, const void *x, const int64_t *x_strides, const void *y,
+                         const int64_t *y_strides, void *out, const int64_t *out_strides, const int64_t *shape,
+                         const int64_t *start, const int64_t *nmesh, double scale, int32_t conj_y, int32_t accumulate,
+                         int32_t deconv_pow, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -374,6 +374,36 @@ class HipBackend(object):
                   _byte_strides(acc), _abi.i64arr(v.shape, 3), _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3),
                   _abi.f64arr(shift, 3), float(a), float(b), int(deconv_pow), self.stream())
 
+    # -- binned correlation function ------------------------------------------
+    def corr_project(self, params, x, start, nmesh, boxsize, redges, muedges, acc):
+        """add the binned sums of the local real block `x` over the separations of its cells into the float64 device
+        vector `acc` (layout: include/pmesh_amd.h, pmx_corr_project)"""
+        if x.numel() == 0:
+            return
+        self.call('corr_project', C.byref(params), x.dim(), x.element_size(), x.data_ptr(), _byte_strides(x),
+                  _abi.i64arr(x.shape, 3), *_mesh_args(start, nmesh, boxsize), redges.data_ptr(),
+                  muedges.data_ptr() if muedges is not None else None, acc.data_ptr(), self.stream())
+
+    def corr_vjp(self, params, g, start, nmesh, boxsize, redges, muedges, coef):
+        """every cell of the local real block `g` (may be raw memory) = the adjoint of corr_project for the coefficient
+        table `coef`, a float64 device vector (layout: include/pmesh_amd.h, pmx_corr_vjp)"""
+        if g.numel() == 0:
+            return
+        self.call('corr_vjp', C.byref(params), g.dim(), g.element_size(), g.data_ptr(), _byte_strides(g),
+                  _abi.i64arr(g.shape, 3), *_mesh_args(start, nmesh, boxsize), redges.data_ptr(),
+                  muedges.data_ptr() if muedges is not None else None, coef.data_ptr(), self.stream())
+
+    def spectral_product(self, x, y, out, start, nmesh, scale=1.0, conj_y=False, accumulate=False, deconv_pow=0):
+        """out = [out +] scale * x * (conj(y) or y) / prod_d sinc(w_d / 2)^deconv_pow over the local complex blocks
+        (pmx_spectral_product); out may be x or y itself, and without `accumulate` raw memory"""
+        if x.numel() == 0:
+            return
+        es = x.element_size()
+        self.call('spectral_product', x.dim(), es // 2, x.data_ptr(), _byte_strides(x), y.data_ptr(), _byte_strides(y),
+                  out.data_ptr(), _byte_strides(out), _abi.i64arr(x.shape, 3), _abi.i64arr(start, 3),
+                  _abi.i64arr(nmesh, 3), float(scale), int(bool(conj_y)), int(bool(accumulate)), int(deconv_pow),
+                  self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""

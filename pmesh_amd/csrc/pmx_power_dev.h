@@ -157,6 +157,35 @@ __device__ __forceinline__ void legendre_poles(const PParams &P, double mu, doub
     }
 }
 
+// ---- the real side (pmx_corr.hip): a tile of a real mesh binned by the separation of its cells --------------------
+
+// one real element of f4 / f8 storage, as a double
+template <typename T> __device__ __forceinline__ double real_get(const char *p) { return (double)*(const T *)p; }
+template <typename T> __device__ __forceinline__ void real_put(char *p, double v) { *(T *)p = (T)v; }
+
+// r_d = (s * L) / N of global index gi (counted negative at and beyond N / 2): the Python expression
+// `signed * BoxSize[d] / Nmesh[d]` of pm.py:_block_coords, what RealField.x holds on an f8 mesh
+__device__ __forceinline__ double cell_r(int64_t gi, int64_t n, double nd, double L)
+{
+    double s = (double)gi;
+    if (gi >= n / 2) s -= nd;
+    return (s * L) / nd;
+}
+
+// tile_axis on the real side: lane's r_d along memory-order axis `ax` of the tile into rax, and the extreme |r_d| over
+// the tile's index box into ext2 (min, max; a tile that straddles N / 2 holds both signs, the extremes are taken over
+// its cells)
+__device__ __forceinline__ void tile_axis_real(const PGeom &g, int ax, int lane, int ext, int64_t o, double *rax,
+                                               double *ext2)
+{
+    double r = 0;
+    if (lane < ext && g.on[ax]) r = cell_r(g.start[ax] + o + lane, g.nmesh[ax], g.nl_n[ax], g.boxsize[ax]);
+    rax[ax * 64 + lane] = r;
+    const bool in = lane < ext;
+    const double mn = wave_min(in ? fabs(r) : INFINITY), mx = wave_max(in ? fabs(r) : 0.0);
+    if (lane == 0) { ext2[0] = mn; ext2[1] = mx; }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------
 
 // Checks the arguments the forward and the adjoint share and fills the kernel parameters: per_bin / per_cell doubles

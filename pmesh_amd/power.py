@@ -71,6 +71,34 @@ def _complex(field):
     return field
 
 
+def _binning(ndim, name, edges, muedges, los, poles):
+    """the checked bin edges `name` (kedges; redges on the real side), mu edges (or None), multipole orders and unit
+    line of sight of a binned two-point statistic on a mesh of ndim dimensions"""
+    ke = _edges(name, edges)
+    if len(ke) - 1 > _abi.PMX_POWER_MAX_KBINS:
+        raise ValueError('%d %s bins: more than PMX_POWER_MAX_KBINS = %d'
+                         % (len(ke) - 1, name[0], _abi.PMX_POWER_MAX_KBINS))
+    me = None
+    if muedges is not None:
+        me = _edges('muedges', muedges, -1.0, 1.0)
+        if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
+            raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d'
+                             % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
+    ells = [int(ell) for ell in poles]
+    if len(ells) > _abi.PMX_POWER_MAX_POLES:
+        raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
+    if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
+        raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
+    if los is None:
+        los = numpy.zeros(ndim)
+        los[-1] = 1.0
+    los = numpy.array(los, dtype='f8').reshape(-1)
+    norm = numpy.sqrt((los ** 2).sum())
+    if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
+        raise ValueError('los must be a nonzero vector of %d components' % ndim)
+    return ke, me, ells, los / norm
+
+
 class _Plan(object):
     """the checked arguments of one spectrum: the fields, the edges, the multipole orders and the pmx_power struct"""
 
@@ -90,30 +118,9 @@ class _Plan(object):
         if a.value.dtype not in (torch.complex64, torch.complex128):
             raise ValueError('power_spectrum measures complex64 or complex128 fields')
 
-        ke = _edges('kedges', kedges)
-        if len(ke) - 1 > _abi.PMX_POWER_MAX_KBINS:
-            raise ValueError('%d k bins: more than PMX_POWER_MAX_KBINS = %d' % (len(ke) - 1, _abi.PMX_POWER_MAX_KBINS))
-        me = None
-        if muedges is not None:
-            me = _edges('muedges', muedges, -1.0, 1.0)
-            if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
-                raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d'
-                                 % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
-        ells = [int(ell) for ell in poles]
-        if len(ells) > _abi.PMX_POWER_MAX_POLES:
-            raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
-        if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
-            raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
+        ke, me, ells, los = _binning(ndim, 'kedges', kedges, muedges, los, poles)
         if int(deconv_pow) != deconv_pow or deconv_pow < 0:
             raise ValueError('deconv_pow must be a non-negative integer')
-        if los is None:
-            los = numpy.zeros(ndim)
-            los[-1] = 1.0
-        los = numpy.array(los, dtype='f8').reshape(-1)
-        norm = numpy.sqrt((los ** 2).sum())
-        if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
-            raise ValueError('los must be a nonzero vector of %d components' % ndim)
-        los = los / norm
 
         p = _abi.Power()
         p.nk = len(ke) - 1
