@@ -837,6 +837,69 @@ int pmx_spectral_product(int32_t ndim, int32_t elsize, const void *x, const int6
                          const int64_t *start, const int64_t *nmesh, double scale, int32_t conj_y, int32_t accumulate,
                          int32_t deconv_pow, void *stream);
 
+/* ---- Poisson-sampled particles from a real mesh (what nbodykit's LogNormalCatalog does on the host: Poisson counts of
+ * the cells, the cell coordinates repeated, uniform offsets; pmesh_amd.mock) ---------------------------------------------
+ * The sampling rule.  Every random number is one call of Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53,
+ * 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85) with
+ *     key = (seed & 0xffffffff, seed >> 32),     counter = (g & 0xffffffff, g >> 32, j, stream)
+ * where g is the GLOBAL C-order index of the cell over nmesh, (i_0 N_1 + i_1) N_2 + i_2 (likewise in 1-d and 2-d): a
+ * cell's draws depend on no block, rank or launch shape.  Its words are w_0 .. w_3.
+ *   rate     in double whatever the field's element type: lam = scale * x (PMX_POISSON_LINEAR) or
+ *            lam = scale * exp(bias * x) (PMX_POISSON_EXP).  A cell whose lam is NaN, negative, infinite or above
+ *            PMX_POISSON_MAX_RATE gets the count 0 and adds 1 to `flagged`.
+ *   count    (stream 0) n = max(1, ceil(lam / PMX_POISSON_CHUNK_RATE)) chunks of rate lam_j = lam / n; chunk j takes one
+ *            call with counter word j, u = ((w_0 >> 5) * 2^26 + (w_1 >> 6) + 1) * 2^-53 in (0, 1], and is drawn by
+ *            inversion: k = 0; p = exp(-lam_j); s = p; while (u > s && k < PMX_POISSON_MAX_STEPS) { k += 1;
+ *            p = p * lam_j / k; s += p; } (the multiplication and the division each round once).  The count of the
+ *            cell is the sum of its chunks' k, a uint32.
+ *   position (stream 1) particle p of the cell takes one call with j = p; u_d = (w_d + 0.5) * 2^-32 for d < ndim and
+ *            x_d = ((i_d - 0.5) + u_d) * (L_d / N_d), plus L_d where that is negative (and 0 should that sum round to
+ *            L_d): uniform in the cell centred on the grid point i_d L_d / N_d, the convention of the windows here — a
+ *            nearest-grid-point paint of the particles returns the counts.
+ *   order    cells in the C order of the local block, the particles of a cell in the order of p.
+ * The local cells, in C order, are cut into segments of PMX_POISSON_SEGMENT cells — a constant of the ABI, not a launch
+ * parameter — and the four entries are called in this order, on one stream: */
+#define PMX_POISSON_SEGMENT 4096         /* cells per segment */
+#define PMX_POISSON_MAX_RATE (1 << 20)   /* the largest rate of a cell */
+#define PMX_POISSON_CHUNK_RATE 16        /* a cell's rate is drawn in chunks of at most this rate */
+#define PMX_POISSON_MAX_STEPS 128        /* the cap on the search steps of one chunk (P(k > 128 | 16) < 1e-60) */
+#define PMX_POISSON_LINEAR 0             /* mode: lam = scale * x */
+#define PMX_POISSON_EXP 1                /* mode: lam = scale * exp(bias * x) */
+
+/* *total += the sum of the rates (mode, scale, bias as above; refused rates included as they are) of the real block x:
+ * a DEVICE double, one float atomic per segment (the last bits may differ from run to run).  elsize 4 or 8: one real
+ * element, loaded as such and widened to double; any byte strides (C order, a padded last axis, transposed or strided
+ * views).  ndim 1 to 3.  The mean of exp(bias x) of a lognormal mock and the expected number of particles. */
+int pmx_poisson_rate_sum(int32_t ndim, int32_t elsize, const void *x, const int64_t *x_strides, const int64_t *shape,
+                         int32_t mode, double scale, double bias, double *total, void *stream);
+
+/* The counts of the block x (read as in pmx_poisson_rate_sum) at `start` inside the mesh `nmesh`, one lane per cell:
+ *   counts     uint32 per local cell, contiguous in the C order of the block            (DEVICE, prod(shape) entries)
+ *   seg_sums   the sum of the counts of every segment, reduced in LDS   (DEVICE int64, ceil(prod(shape) / SEGMENT))
+ *   flagged    += the number of cells whose rate is refused; the caller zeroes it               (DEVICE int64)
+ * Integer results: deterministic.  Moves elsize + 4 bytes per cell.  PMX_EINVAL for a block that does not lie inside the
+ * mesh, PMX_EUNSUPPORTED for an axis of 2^31 - 4096 cells or more or 2^31 segments. */
+int pmx_poisson_count(int32_t ndim, int32_t elsize, const void *x, const int64_t *x_strides, const int64_t *shape,
+                      const int64_t *start, const int64_t *nmesh, int32_t mode, double scale, double bias,
+                      uint64_t seed, uint32_t *counts, int64_t *seg_sums, int64_t *flagged, void *stream);
+
+/* The exclusive scan of the nseg segment sums, in place: seg_sums[s] becomes the row of the first particle of segment
+ * s, and *total (DEVICE int64) the number of particles.  One workgroup walks the array; no workgroup of this feature
+ * waits on memory written by another.  The host reads *total (and flagged) here to allocate `pos`: the one
+ * synchronisation of the sequence. */
+int pmx_poisson_scan(int64_t *seg_sums, int64_t nseg, int64_t *total, void *stream);
+
+/* The particles.  pos is a C-contiguous DEVICE array of float64, (npart, ndim), npart the *total of the scan; cell, when
+ * not NULL, a DEVICE int64 array of npart entries that receives the global cell index g of every particle.  counts and
+ * seg_offsets are what pmx_poisson_count and pmx_poisson_scan left.  One workgroup per segment scans the segment's
+ * counts in LDS (16 KB) and walks its particles ONE LANE PER PARTICLE: the lane finds its cell by binary search in the
+ * LDS offsets, so consecutive lanes write consecutive rows and a cell of thousands of particles is shared by the whole
+ * workgroup.  Row offsets are 64-bit; a single segment may hold up to 2^32 - 1 particles.  Moves 4 bytes per cell and
+ * 8 ndim (+ 8 with cell) bytes per particle.  Deterministic. */
+int pmx_poisson_emit(int32_t ndim, const int64_t *shape, const int64_t *start, const int64_t *nmesh,
+                     const double *boxsize, uint64_t seed, const uint32_t *counts, const int64_t *seg_offsets,
+                     int64_t npart, double *pos, int64_t *cell, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -404,6 +404,40 @@ class HipBackend(object):
                   _abi.i64arr(nmesh, 3), float(scale), int(bool(conj_y)), int(bool(accumulate)), int(deconv_pow),
                   self.stream())
 
+    # -- Poisson-sampled particles ---------------------------------------------
+    def poisson_rate_sum(self, x, mode, scale, bias, total):
+        """total[0] += the sum of the rates of the local real block `x` (pmx_poisson_rate_sum); total is a float64
+        device tensor of one element"""
+        if x.numel() == 0:
+            return
+        self.call('poisson_rate_sum', x.dim(), x.element_size(), x.data_ptr(), _byte_strides(x),
+                  _abi.i64arr(x.shape, 3), int(mode), float(scale), float(bias), total.data_ptr(), self.stream())
+
+    def poisson_count(self, x, start, nmesh, mode, scale, bias, seed, counts, seg_sums, flagged):
+        """the Poisson counts of the local real block `x` into the contiguous uint32 tensor `counts`, their sums per
+        segment of PMX_POISSON_SEGMENT cells into the int64 tensor `seg_sums`, the number of refused cells added to
+        the int64 tensor `flagged` of one element (pmx_poisson_count)"""
+        if x.numel() == 0:
+            return
+        self.call('poisson_count', x.dim(), x.element_size(), x.data_ptr(), _byte_strides(x), _abi.i64arr(x.shape, 3),
+                  _abi.i64arr(start, 3), _abi.i64arr(nmesh, 3), int(mode), float(scale), float(bias), int(seed),
+                  counts.data_ptr(), seg_sums.data_ptr(), flagged.data_ptr(), self.stream())
+
+    def poisson_scan(self, seg_sums, total):
+        """the exclusive scan of the int64 tensor `seg_sums` in place, its total into the int64 tensor `total` of one
+        element (pmx_poisson_scan)"""
+        self.call('poisson_scan', seg_sums.data_ptr() if seg_sums.numel() else None, seg_sums.numel(),
+                  total.data_ptr(), self.stream())
+
+    def poisson_emit(self, shape, start, nmesh, boxsize, seed, counts, seg_offsets, pos, cell=None):
+        """the particles of the counts into the rows of the (n, ndim) float64 tensor `pos` and, when given, their
+        global cell indices into the int64 tensor `cell` (pmx_poisson_emit)"""
+        if pos.shape[0] == 0:
+            return
+        self.call('poisson_emit', len(shape), _abi.i64arr(shape, 3), *_mesh_args(start, nmesh, boxsize), int(seed),
+                  counts.data_ptr(), seg_offsets.data_ptr(), pos.shape[0], pos.data_ptr(),
+                  cell.data_ptr() if cell is not None else None, self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""
