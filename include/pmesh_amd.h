@@ -900,6 +900,77 @@ int pmx_poisson_emit(int32_t ndim, const int64_t *shape, const int64_t *start, c
                      const double *boxsize, uint64_t seed, const uint32_t *counts, const int64_t *seg_offsets,
                      int64_t npart, double *pos, int64_t *cell, void *stream);
 
+/* ---- friends-of-friends groups of particles (what nbodykit's FOF does on the host with a kd-tree; pmesh_amd.fof) -------
+ * The rule.  Positions are (n, ndim) rows, ndim 1 to 3, float or double (a float is widened exactly); all arithmetic is
+ * in double, every operation rounding once.
+ *   wrap     w_d = x_d - L_d * floor(x_d / L_d), then w_d + L_d where that is negative and 0 where it is >= L_d: rows
+ *            lie in [0, L_d).  A row with a coordinate that is not finite adds 1 to `flagged`.
+ *   friends  two rows are friends when sum_d dx_d^2 <= b^2, dx_d = w_d - w'_d; dx_d -= L_d * rint(dx_d / L_d) (the
+ *            minimum image), the sum accumulated in the order d = 0, 1, 2.  b, the linking length, is finite, positive
+ *            and 2 b <= min_d L_d.
+ *   groups   a group is a connected component of the friendship graph over the rows of all ranks; the canonical label of
+ *            a row is minid, the smallest GLOBAL row index of its group (local index plus the rows of the lower ranks).
+ *            It depends on no decomposition, launch shape or order in which lanes run.
+ * The passes, on the n rows a rank holds (its own and the ghosts within b of its block), all on one stream:
+ *   pmx_fof_cells      wrapped rows, the cell of every row on a grid of cells of side >= b, the rows per cell
+ *   (the caller)       cell_start = the exclusive scan of the counts, ncells + 1 entries
+ *   pmx_fof_fill       the rows in cell order: order[slot] and the wrapped rows sorted
+ *   pmx_fof_link       one lane per row: the friends of lower index in the 3^ndim neighbouring cells, hooked into a
+ *                      lock-free union-find that keeps parent[x] <= x
+ *   pmx_fof_flatten    parent[i] = the root of row i: the smallest local index of its component
+ *   pmx_fof_minlabel   the minimum of an int64 value over every local component, written to all its members
+ *   pmx_fof_group_sums per-label sums of mass, mass x wrapped displacement and mass x velocity (the halo catalogue)
+ * The grid.  Axis d has ncell[d] cells of side extent_d / ncell[d] >= b starting at origin[d]; the cell of a row is
+ * c_d = (int)(r_d * inv_side[d]) clamped to ncell[d] - 1, r_d = w_d - origin[d], plus L_d where that is negative.  A
+ * periodic axis (bit d of `periodic`, PMX_FOF_PERIODIC_X << d) has origin 0 and covers the box: neighbours wrap, and
+ * with 1 or 2 cells every cell is visited once.  An open axis covers extent_d = ncell[d] / inv_side[d] < L_d; nothing
+ * wraps, and a row beyond the extent (rounding) goes to the nearer end cell.  The flat cell index is C order.
+ * n <= PMX_FOF_MAX_ROWS and prod(ncell) <= PMX_FOF_MAX_ROWS: parents, slots and cells are 32-bit. */
+#define PMX_FOF_MAX_ROWS 2147483647      /* rows (own and ghosts) of one rank, and cells of its grid */
+#define PMX_FOF_CELLS_PER_ROW 2          /* the grid a caller lays has at most this many cells per row (and one) */
+#define PMX_FOF_PERIODIC_X 1             /* `periodic`: axis 0 wraps; axis d: PMX_FOF_PERIODIC_X << d */
+
+/* wpos[i, d] = the wrapped row i (DEVICE double, (n, ndim) contiguous), cell_of[i] its flat cell (DEVICE int32),
+ * counts[c] += 1 per row of cell c (DEVICE int32, prod(ncell) entries, zeroed by the caller), *flagged += the rows
+ * with a coordinate that is not finite (DEVICE int64; such a row lands in some valid cell).  pos: n rows of ndim
+ * columns, any strides.  Moves ndim * elsize + 8 ndim + 4 bytes per row and one atomic. */
+int pmx_fof_cells(int32_t ndim, const pmx_vec *pos, int64_t n, const double *boxsize, const double *origin,
+                  const double *inv_side, const int64_t *ncell, int32_t periodic, double *wpos, int32_t *cell_of,
+                  int32_t *counts, int64_t *flagged, void *stream);
+
+/* order[slot] = i and spos[slot, :] = wpos[i, :] with slot = cell_start[cell_of[i]] + (cursor[cell_of[i]]++): the rows
+ * in cell order.  cursor: DEVICE int32, ncells entries, zeroed by the caller.  The order of the rows INSIDE a cell
+ * depends on the atomics; nothing the later passes leave depends on it. */
+int pmx_fof_fill(int32_t ndim, int64_t n, const double *wpos, const int32_t *cell_of, const int32_t *cell_start,
+                 int32_t *cursor, int32_t *order, double *spos, void *stream);
+
+/* parent[i] = i for every row, then one lane per slot k (row i = order[k]): every row j < i of the 3^ndim neighbouring
+ * cells that is a friend of i is united with it: find both roots; atomic-min the smaller root into the larger root's
+ * slot; if the value returned was not that root, go on with the value returned.  Every loop walks strictly decreasing
+ * indices; no lane waits for another.  b2 = b * b.  Afterwards two rows are in one component exactly if their parent
+ * chains end at the same root. */
+int pmx_fof_link(int32_t ndim, int64_t n, const double *spos, const int32_t *order, const int32_t *cell_of,
+                 const int32_t *cell_start, const int64_t *ncell, int32_t periodic, const double *boxsize, double b2,
+                 int32_t *parent, void *stream);
+
+/* parent[i] = the root of row i (the smallest local index of its component), in place, a launch of its own */
+int pmx_fof_flatten(int64_t n, int32_t *parent, void *stream);
+
+/* val[i] = min over the rows j with root[j] == root[i] of val[j] (DEVICE int64, in place); *changed += the number of
+ * rows whose value changed (DEVICE int64).  work: DEVICE int64 scratch of n entries.  root: what pmx_fof_flatten
+ * left.  One copy, one atomic minimum per row that is not a root, one gather. */
+int pmx_fof_minlabel(int64_t n, const int32_t *root, int64_t *val, int64_t *work, int64_t *changed, void *stream);
+
+/* out[l, :] += over the rows i with l = labels[i] in 1 .. ngroups of (m_i, m_i * dx_i[0 .. ndim), m_i * v_i[0 .. ndim)):
+ * out is a DEVICE double array (ngroups + 1, 1 + 2 ndim), zeroed by the caller; dx_i the minimum image of
+ * wrap(pos_i) - wrap(ref[l, :]), ref a DEVICE double array (ngroups + 1, ndim) contiguous: the position of the
+ * reference member of every group.  mass (one column; NULL: 1) and vel (ndim columns; NULL: 0) are optional.  Equal
+ * labels are reduced within a wave before one atomic per wave, label and column: the members of a large halo do not
+ * meet on one line.  The last bits depend on the order of the atomics. */
+int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_t *labels, const pmx_vec *mass,
+                       const pmx_vec *vel, const double *ref, int64_t ngroups, const double *boxsize, double *out,
+                       void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

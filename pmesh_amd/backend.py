@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import _abi
+from . import _abi, _arrays
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBNAME = 'libpmesh_amd.so'
@@ -437,6 +437,56 @@ class HipBackend(object):
         self.call('poisson_emit', len(shape), _abi.i64arr(shape, 3), *_mesh_args(start, nmesh, boxsize), int(seed),
                   counts.data_ptr(), seg_offsets.data_ptr(), pos.shape[0], pos.data_ptr(),
                   cell.data_ptr() if cell is not None else None, self.stream())
+
+    # -- friends-of-friends groups -----------------------------------------------
+    def fof_cells(self, pos, boxsize, origin, inv_side, ncell, periodic, wpos, cell_of, counts, flagged):
+        """the wrapped rows of the (n, ndim) tensor `pos` into `wpos` (float64), their flat cells into `cell_of`
+        (int32), the rows per cell added to the zeroed `counts` (int32), the rows that are not finite to the int64
+        tensor `flagged` of one element (pmx_fof_cells)"""
+        if pos.shape[0] == 0:
+            return
+        pv = _arrays.vec(pos)
+        self.call('fof_cells', len(ncell), C.byref(pv), pos.shape[0], _abi.f64arr(boxsize, 3), _abi.f64arr(origin, 3),
+                  _abi.f64arr(inv_side, 3), _abi.i64arr(ncell, 3), int(periodic), wpos.data_ptr(), cell_of.data_ptr(),
+                  counts.data_ptr(), flagged.data_ptr(), self.stream())
+
+    def fof_fill(self, wpos, cell_of, cell_start, cursor, order, spos):
+        """the rows in cell order: `order` (int32) and the wrapped rows sorted into `spos`; `cursor` is a zeroed int32
+        tensor of one entry per cell (pmx_fof_fill)"""
+        if wpos.shape[0] == 0:
+            return
+        self.call('fof_fill', wpos.shape[1], wpos.shape[0], wpos.data_ptr(), cell_of.data_ptr(), cell_start.data_ptr(),
+                  cursor.data_ptr(), order.data_ptr(), spos.data_ptr(), self.stream())
+
+    def fof_link(self, spos, order, cell_of, cell_start, ncell, periodic, boxsize, b2, parent):
+        """the union-find of the friends into the int32 tensor `parent` (pmx_fof_link)"""
+        if spos.shape[0] == 0:
+            return
+        self.call('fof_link', spos.shape[1], spos.shape[0], spos.data_ptr(), order.data_ptr(), cell_of.data_ptr(),
+                  cell_start.data_ptr(), _abi.i64arr(ncell, 3), int(periodic), _abi.f64arr(boxsize, 3), float(b2),
+                  parent.data_ptr(), self.stream())
+
+    def fof_flatten(self, parent):
+        """parent[i] = the root of row i, in place (pmx_fof_flatten)"""
+        if parent.numel():
+            self.call('fof_flatten', parent.numel(), parent.data_ptr(), self.stream())
+
+    def fof_minlabel(self, root, val, work, changed):
+        """the int64 tensor `val` replaced by its minimum over every component of `root`, the number of rows that
+        changed added to the int64 tensor `changed` of one element; `work` is int64 scratch (pmx_fof_minlabel)"""
+        if val.numel():
+            self.call('fof_minlabel', val.numel(), root.data_ptr(), val.data_ptr(), work.data_ptr(),
+                      changed.data_ptr(), self.stream())
+
+    def fof_group_sums(self, pos, labels, mass, vel, ref, boxsize, out):
+        """the sums per label of (mass, mass x displacement from ref, mass x vel) added into the zeroed float64 tensor
+        `out` of shape (ngroups + 1, 1 + 2 ndim) (pmx_fof_group_sums)"""
+        if pos.shape[0] == 0 or out.shape[0] <= 1:
+            return
+        pv, mv, vv = _arrays.vec(pos), _arrays.vec(mass), _arrays.vec(vel)
+        self.call('fof_group_sums', ref.shape[1], pos.shape[0], C.byref(pv), labels.data_ptr(),
+                  C.byref(mv) if mass is not None else None, C.byref(vv) if vel is not None else None,
+                  ref.data_ptr(), out.shape[0] - 1, _abi.f64arr(boxsize, 3), out.data_ptr(), self.stream())
 
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v

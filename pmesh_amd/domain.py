@@ -315,6 +315,11 @@ class Layout(object):
             self._memo = (memo_key, data, r)
         return r
 
+    def forget(self):
+        """drop the remembered result of the last exchange: for a caller that exchanges new values every round from
+        tensors that may share an address (all empty tensors do)"""
+        self._memo = None
+
     def _exchange_packed(self, args):
         """exchange(pack=True): the gathered rows of every array side by side in one byte row per
         item, one all-to-all-v for all of them (domain.py:161-166, pack_arrays).  Every column is gathered
@@ -619,10 +624,12 @@ class Layout(object):
         """
         Pull the data from other ranks back to its original hosting rank (domain.py:208-318).
 
-        mode : 'sum', 'any', 'mean', 'all', 'local'
+        mode : 'sum', 'any', 'mean', 'all', 'local', 'min'
             'all' returns all results, local and ghosts, without any reduction;
             'sum' reduces the ghosts to the local with sum; 'local' keeps only the local
-            copy; 'any' uses any one of local or ghost; 'mean' the mean over copies.
+            copy; 'any' uses any one of local or ghost; 'mean' the mean over copies;
+            'min' the minimum over copies, on the device (what mode=numpy.minimum computes
+            through the host: the label merge of pmesh_amd.fof).
         """
         be = backend.get()
         data = promote(data, self.comm)
@@ -678,6 +685,12 @@ class Layout(object):
         if mode == 'any':
             res = torch.zeros((self.sendlength,) + trailing, dtype=data.dtype, device=be.device)
             res[self.indices.to(torch.int64)] = recvbuffer
+            return finish(res)
+        if mode == 'min':
+            # every item has at least one copy (its own row or a ghost); amin without the initial value
+            res = torch.empty((self.sendlength,) + trailing, dtype=data.dtype, device=be.device)
+            idx = self.indices.to(torch.int64).reshape([-1] + [1] * (recvbuffer.dim() - 1)).expand_as(recvbuffer)
+            res.scatter_reduce_(0, idx, recvbuffer, 'amin', include_self=False)
             return finish(res)
         if isinstance(mode, numpy.ufunc):
             # host path: ufunc.reduceat over index-sorted copies (domain.py:297-303)
