@@ -28,80 +28,39 @@ Definition, for a 1-, 2- or 3-d real mesh (f4 or f8) with the spectra a and b (b
 import numpy
 import torch
 
-from . import _abi, backend
-from .power import _binning, _cotangent, _same_layout
+from . import backend
+from .power import (_Binning, _Result, _blank_like, _jvp_terms, _ndim, _same_layout, _same_mesh,
+                    _unsupported_is_value_error)
 
 
-class CorrResult(object):
+class CorrResult(_Result):
     """The binned mesh.  1-d bins (Nr): ``redges``, ``r`` (mean |r|), ``modes`` (count), ``corr`` (real), ``poles``
     (dict ell -> real array).  (r, mu) bins (Nr x Nmu), None without ``muedges``: ``muedges``, ``r2d``, ``mu2d``,
     ``modes2d``, ``corr2d``.  Means are sums over the count; empty bins hold NaN."""
-
-    def __init__(self, redges, muedges, acc, ells):
-        nr = len(redges) - 1
-        s1 = 3 + len(ells)
-        a1 = acc[:nr * s1].reshape(nr, s1)
-        self.redges = redges
-        self.muedges = muedges
-        with numpy.errstate(invalid='ignore', divide='ignore'):
-            n = a1[:, 0]
-            self.modes = numpy.rint(n).astype('i8')
-            self.r = a1[:, 1] / n
-            self.corr = a1[:, 2] / n
-            self.poles = {ell: (2 * ell + 1) * a1[:, 3 + p] / n for p, ell in enumerate(ells)}
-            self.r2d = self.mu2d = self.modes2d = self.corr2d = None
-            if muedges is not None:
-                a2 = acc[nr * s1:].reshape(nr, len(muedges) - 1, 4)
-                n2 = a2[..., 0]
-                self.modes2d = numpy.rint(n2).astype('i8')
-                self.r2d = a2[..., 1] / n2
-                self.mu2d = a2[..., 2] / n2
-                self.corr2d = a2[..., 3] / n2
+    _x, _v, _width = 'r', 'corr', 1
 
 
-class _Bins(object):
-    """the checked binning of a real mesh of `pm`: the edges, the multipole orders and the pmx_power struct"""
+class _Bins(_Binning):
+    """the checked binning of a real mesh of `pm`"""
 
     def __init__(self, pm, redges, muedges, los, poles):
-        ndim = len(pm.Nmesh)
-        if ndim > _abi.PMX_MAXDIM:
-            raise NotImplementedError('correlation functions of meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
-        re, me, ells, los = _binning(ndim, 'redges', redges, muedges, los, poles)
-        p = _abi.Power()
-        p.nk = len(re) - 1
-        p.nmu = 0 if me is None else len(me) - 1
-        p.npoles = len(ells)
-        for i, ell in enumerate(ells):
-            p.poles[i] = ell
-        p.hermitian = 0
-        p.deconv_pow = 0
-        p.volume = 1.0
-        for d in range(ndim):
-            p.los[d] = float(los[d])
-        self.pm, self.p, self.re, self.me, self.ells = pm, p, re, me, ells
-        self.s1 = 3 + len(ells)
-        be = backend.get()
-        self.rt = torch.from_numpy(re).to(be.device)
-        self.mt = torch.from_numpy(me).to(be.device) if me is not None else None
+        _Binning.__init__(self, _ndim(pm, 'correlation functions'), 'redges', redges, muedges, los, poles, CorrResult,
+                          comm=pm.comm)
+        self.pm = pm
 
     def sums(self, field):
-        """the raw sums of pmx_corr_project for the RealField `field`, summed over the ranks: a host vector"""
-        be = backend.get()
-        p = self.p
-        acc = torch.zeros(p.nk * self.s1 + p.nk * p.nmu * 4, dtype=torch.float64, device=be.device)
-        try:
-            be.corr_project(p, field.value, field.start, self.pm.Nmesh, self.pm.BoxSize, self.rt, self.mt, acc)
-        except backend.PmxError as e:
-            if e.code == _abi.PMX_EUNSUPPORTED:
-                raise ValueError(str(e))
-            raise
-        # one sum over the ranks of the raw sums, then the division
-        if self.pm.comm.size > 1:
-            acc = self.pm.comm.allreduce(acc)
-        return acc.cpu().numpy()
+        """the raw sums of pmx_corr_project for the RealField `field`"""
+        return _Binning.sums(self, lambda acc: backend.get().corr_project(
+            self.p, field.value, field.start, self.pm.Nmesh, self.pm.BoxSize, self.et, self.mt, acc))
 
-    def result(self, acc):
-        return CorrResult(self.re, self.me, acc, self.ells)
+    def measure(self, field):
+        return self.unpack(self.sums(field))
+
+    def measure_zero(self, like):
+        """the counts and means of the binning alone: they depend on the geometry, the projection of any mesh has them"""
+        zero = _blank_like(like, 'real')
+        zero.value[...] = 0
+        return self.measure(zero)
 
 
 def _real(field):
@@ -123,8 +82,7 @@ def bin_real(field, redges, muedges=None, los=None, poles=()):
     poles : multipole orders, each in 0..PMX_POWER_MAX_ELL, at most PMX_POWER_MAX_POLES of them.
     """
     field = _real(field)
-    bins = _Bins(field.pm, redges, muedges, los, poles)
-    return bins.result(bins.sums(field))
+    return _Bins(field.pm, redges, muedges, los, poles).measure(field)
 
 
 # ---- the correlation mesh --------------------------------------------------------------------------------------------
@@ -149,27 +107,15 @@ def _pair(field, other, deconv_pow, real_ok):
         return f, False
     if int(deconv_pow) != deconv_pow or deconv_pow < 0:
         raise ValueError('deconv_pow must be a non-negative integer')
-    pm = getattr(field, 'pm', None)
-    if pm is not None and len(pm.Nmesh) > _abi.PMX_MAXDIM:
-        raise NotImplementedError('correlation functions of meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
+    if getattr(field, 'pm', None) is not None:
+        _ndim(field.pm, 'correlation functions')
     a, mine_a = spectrum(field)
     b, mine_b = None, False
     if other is not None:
         b, mine_b = spectrum(other)
-        pm = a.pm
-        if b.pm is not pm and (tuple(b.pm.Nmesh) != tuple(pm.Nmesh) or tuple(b.pm.BoxSize) != tuple(pm.BoxSize)
-                               or b.pm.comm is not pm.comm):
-            raise ValueError('the two fields belong to different meshes')
+        _same_mesh(a, b)
         _same_layout(a, b)
     return a, b, mine_a, mine_b
-
-
-def _blank_like(f):
-    """a new field of f's type; raw memory on the device, where the kernels write every element of it"""
-    from .pm import _blank
-    if backend.get().name == 'hip' and f.value.numel():
-        return _blank(type(f), f.pm)
-    return f.pm.create(type=type(f))
 
 
 def _product(x, y, out, conj_y=False, accumulate=False, deconv_pow=0):
@@ -212,17 +158,10 @@ def correlation_function(field, redges, other=None, muedges=None, los=None, pole
         raise TypeError('correlation_function measures RealField or ComplexField objects, not %s'
                         % type(field).__name__)
     bins = _Bins(field.pm, redges, muedges, los, poles)         # (the binning is checked before anything is computed)
-    return bins.result(bins.sums(correlation_field(field, other, deconv_pow)))
+    return bins.measure(correlation_field(field, other, deconv_pow))
 
 
 # ---- gradients -----------------------------------------------------------------------------------------------------
-
-def _real_cotangent(name, v, shape):
-    v = _cotangent(name, v, shape)
-    if (v.imag != 0).any():
-        raise ValueError('%s must be real: the correlation function is' % name)
-    return v.real
-
 
 def correlation_function_vjp(field, redges, v_corr=None, v_poles=None, v_corr2d=None, other=None, muedges=None,
                              los=None, poles=(), deconv_pow=0, result=None):
@@ -245,46 +184,10 @@ def correlation_function_vjp(field, redges, v_corr=None, v_poles=None, v_corr2d=
     a, b, _, _ = _pair(field, other, deconv_pow, False)
     pm = a.pm
     bins = _Bins(pm, redges, muedges, los, poles)
-    nr, nmu, ells = bins.p.nk, bins.p.nmu, bins.ells
-    if v_corr2d is not None and bins.me is None:
-        raise ValueError('v_corr2d needs muedges')
-    v_poles = dict(v_poles) if v_poles else {}
-    unknown = [ell for ell in v_poles if ell not in ells]
-    if unknown:
-        raise ValueError('v_poles has orders %s that are not among poles %s' % (unknown, ells))
-    v1 = _real_cotangent('v_corr', v_corr, (nr,))
-    vp = [_real_cotangent('v_poles[%d]' % ell, v_poles.get(ell), (nr,)) for ell in ells]
-    v2 = _real_cotangent('v_corr2d', v_corr2d, (nr, nmu)) if nmu else None
-
-    g = _new_real(pm)
-    if result is None:
-        # the counts depend on the geometry alone: the projection of any mesh has them
-        g.value[...] = 0
-        result = bins.result(bins.sums(g))
-    elif tuple(result.modes.shape) != (nr,) or (nmu > 0) != (result.modes2d is not None) or \
-            (nmu and tuple(result.modes2d.shape) != (nr, nmu)):
-        raise ValueError('result is not the CorrResult of these arguments')
-
-    # the coefficient table: acc's layout without the count, |r| and mu columns
-    sc = 1 + len(ells)
-    coef = numpy.zeros(nr * sc + nr * nmu)
-    c1 = coef[:nr * sc].reshape(nr, sc)
-    inv = numpy.where(result.modes > 0, 1.0 / numpy.maximum(result.modes, 1), 0.0)
-    c1[:, 0] = v1 * inv
-    for i, (ell, v) in enumerate(zip(ells, vp)):
-        c1[:, 1 + i] = (2 * ell + 1) * v * inv
-    if nmu:
-        inv2 = numpy.where(result.modes2d > 0, 1.0 / numpy.maximum(result.modes2d, 1), 0.0)
-        coef[nr * sc:].reshape(nr, nmu)[...] = v2 * inv2
-
-    be = backend.get()
-    try:
-        be.corr_vjp(bins.p, g.value, g.start, pm.Nmesh, pm.BoxSize, bins.rt, bins.mt,
-                    torch.from_numpy(coef).to(be.device))
-    except backend.PmxError as e:
-        if e.code == _abi.PMX_EUNSUPPORTED:
-            raise ValueError(str(e))
-        raise
+    coef = bins.coefficients(v_corr, v_poles, v_corr2d, result, lambda: bins.measure_zero(a), real=True)
+    g = _blank_like(a, 'real')
+    _unsupported_is_value_error(backend.get().corr_vjp, bins.p, g.value, g.start, pm.Nmesh, pm.BoxSize, bins.et, bins.mt,
+                                coef)
     from .lpt import _spectrum_of
     G = _spectrum_of(g, a)                                     # r2c over g's own buffer, in the layout of a
     G.value[...] *= float(numpy.prod(pm.Nmesh ** 1.0))         # (RealField.c2r_vjp)
@@ -296,11 +199,6 @@ def correlation_function_vjp(field, redges, v_corr=None, v_poles=None, v_corr2d=
     return ga, _product(a, G, G, conj_y=True, deconv_pow=dp)   # grad_b over the buffer of G
 
 
-def _new_real(pm):
-    from .pm import RealField, _blank
-    return _blank(RealField, pm) if backend.get().name == 'hip' else RealField(pm)
-
-
 def correlation_function_jvp(field, redges, v_field=None, v_other=None, other=None, muedges=None, los=None, poles=(),
                              deconv_pow=0):
     """The tangent of correlation_function along v_field (and v_other): a CorrResult whose ``corr``, ``poles`` and
@@ -310,24 +208,11 @@ def correlation_function_jvp(field, redges, v_field=None, v_other=None, other=No
     accumulating, one c2r and one projection (for the auto correlation b = a and db = da).
     v_field, v_other : ComplexField objects of the fields' layout; None counts as zero."""
     a, b, _, _ = _pair(field, other, deconv_pow, False)
-    if v_other is not None and b is None:
-        raise ValueError('v_other needs other')
+    terms = _jvp_terms(a, b, v_field, v_other, lambda v: _pair(v, None, 0, False)[0])
     bins = _Bins(a.pm, redges, muedges, los, poles)
-    dp = int(deconv_pow)
-    terms = []
-    for v, first in ((v_field, True), (v_other, False)):
-        if v is None:
-            continue
-        v, _, _, _ = _pair(v, None, 0, False)
-        _same_layout(a, v)
-        terms.append((v, b if b is not None else a) if first else (a, v))
-    if b is None and terms:
-        terms.append((a, terms[0][0]))                          # a conj(da): the second half of the auto tangent
     if not terms:
-        zero = _new_real(a.pm)
-        zero.value[...] = 0
-        return bins.result(bins.sums(zero))                     # the counts and means of the forward, zero tangents
+        return bins.measure_zero(a)                             # the forward's counts and means, zero tangents
     scratch = _blank_like(a)
     for n, (x, y) in enumerate(terms):
-        _product(x, y, scratch, conj_y=True, accumulate=n > 0, deconv_pow=dp)
-    return bins.result(bins.sums(scratch.c2r(out=Ellipsis)))
+        _product(x, y, scratch, conj_y=True, accumulate=n > 0, deconv_pow=int(deconv_pow))
+    return bins.measure(scratch.c2r(out=Ellipsis))

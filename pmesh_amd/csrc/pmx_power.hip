@@ -12,6 +12,10 @@
 // rows in sequence and sums runs of modes that fall in the same bin (cell) in registers, so the LDS atomics happen
 // once per run instead of once per mode; the window is added to the global accumulator once per tile, bins that
 // received nothing skipped.
+//
+// The tile walk — LDS layout, tile prologue, row split, window loop, run sums, Hermitian weight, sinc division and the
+// <T, MU, POLES> launch — is the skeleton of pmx_power_dev.h, shared with power_vjp_kernel, corr_kernel and
+// corr_vjp_kernel; this file keeps what a mode contributes and to which sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -20,114 +24,60 @@
 
 namespace pmx {
 
-// the running sums of one thread for one key (a k bin, or a (k, mu) cell)
-template <int N> struct Run {
-    int key;
-    double s[N];
-    __device__ __forceinline__ void reset(int k)
-    {
-        key = k;
-#pragma unroll
-        for (int i = 0; i < N; i++) s[i] = 0;
-    }
-    __device__ __forceinline__ void flush(double *tab, int stride, int n)
-    {
-        if (key < 0) return;
-        double *t = tab + key * stride;
-#pragma unroll
-        for (int i = 0; i < N; i++)
-            if (i < n) atomicAdd(t + i, s[i]);
-    }
-};
-
 template <typename T, bool MU, bool POLES>
 __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const char *__restrict__ a,
                                                        const char *__restrict__ b, const double *__restrict__ kedges,
                                                        const double *__restrict__ muedges, double *__restrict__ acc)
 {
     extern __shared__ double sm[];
-    double *kax = sm;                               // [3][64]  k_d along each memory-order axis of the tile
-    double *sax = sm + PAXIS;                       // [3][64]  sinc(w_d/2)^deconv_pow
-    double *smu = sm + 2 * PAXIS;                   // nmu + 1
-    double *sed = smu + (MU ? P.nmu + 1 : 0);       // window + 1 k edges
-    double *t1 = sed + P.window + 1;                // window * s1
-    double *t2 = t1 + P.window * P.s1;              // window * nmu * 5
-    __shared__ double s_ext[3][2];
-    __shared__ int s_range[2];
+    const PLds L = lds_layout<MU>(sm, P);           // t1: window * s1 sums, t2: window * nmu * 5
+    const PTile t = tile_begin<false, MU>(P, g, L, kedges, muedges);
+    if (t.bhi < t.blo) return;
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int64_t tile = blockIdx.x;
-    const int c2 = (int)(tile % g.nt[2]);
-    tile /= g.nt[2];
-    const int c1 = (int)(tile % g.nt[1]), c0 = (int)(tile / g.nt[1]);
-    const int64_t o[3] = {(int64_t)c0 * PT0, (int64_t)c1 * PT1, (int64_t)c2 * PT2};
-    const int ext[3] = {(int)min((int64_t)PT0, g.shape[0] - o[0]), (int)min((int64_t)PT1, g.shape[1] - o[1]),
-                        (int)min((int64_t)PT2, g.shape[2] - o[2])};
-
-    // per-axis tables of the tile and the extreme |k_d| over its index box (waves 0, 1, 2: one axis each)
-    if (wv < 3) {
-        tile_axis(P, g, wv, lane, ext[wv], o[wv], kax, sax, s_ext[wv]);
-    } else if (MU) {
-        for (int i = lane; i <= P.nmu; i += 64) smu[i] = muedges[i];
-    }
-    __syncthreads();
-    if (wv < 2) {
-        const int j = tile_bin_range(P, g, wv, lane, s_ext, kedges);
-        if (lane == 0) s_range[wv] = j;
-    }
-    __syncthreads();
-    const int blo = s_range[0], bhi = s_range[1];
-    if (bhi < blo) return;
-
-    const double ke0 = kedges[0], kinv = P.nk / (kedges[P.nk] - kedges[0]);
-    const double minv = MU ? P.nmu / (smu[P.nmu] - smu[0]) : 0;
-    const int nrows = ext[0] * ext[1];
-    const int rper = (nrows + 3) / 4;
-    const int r0 = wv * rper, r1 = min(nrows, r0 + rper);
-    const bool lane_on = lane < ext[2];
-    const double k2ax = kax[2 * 64 + lane], s2ax = sax[2 * 64 + lane];
-    const int64_t offa2 = (o[2] + lane) * g.sa[2], offb2 = (o[2] + lane) * g.sb[2];
+    const int lane = threadIdx.x & 63;
+    const PGuess q = bin_guess<MU>(P, L, kedges);
+    const PRows w = wave_rows(t);
+    const double k2ax = L.kax[2 * 64 + lane], s2ax = L.sax[2 * 64 + lane];
+    const int64_t offa2 = lane_off(t, g.sa), offb2 = lane_off(t, g.sb);
     const int s1 = P.s1, nmu = P.nmu;
     int64_t ilast_fixed = -1;
-    if (g.alast == 2) ilast_fixed = g.start[2] + o[2] + lane;
+    if (g.alast == 2) ilast_fixed = g.start[2] + t.o[2] + lane;
 
-    for (int wlo = blo; wlo <= bhi; wlo += P.window) {
-        const int nb = min(P.window, bhi - wlo + 1);
-        for (int i = tid; i < nb * s1; i += PBLOCK) t1[i] = 0;
-        if (MU)
-            for (int i = tid; i < nb * nmu * 5; i += PBLOCK) t2[i] = 0;
-        for (int i = tid; i <= nb; i += PBLOCK) sed[i] = kedges[wlo + i];
+    for (int wlo = t.blo; wlo <= t.bhi; wlo += P.window) {
+        const int nb = window_edges(P, t, wlo, L.sed, kedges);
+        window_zero(L.t1, nb * s1);
+        if (MU) window_zero(L.t2, nb * nmu * 5);
         __syncthreads();
-        const double wk0 = sed[0], wk1 = sed[nb];
+        const double wk0 = L.sed[0], wk1 = L.sed[nb];
 
         Run<POLES ? 4 + 2 * PMX_POWER_MAX_POLES : 4> r1d;
         Run<5> rp, rm;
         r1d.reset(-1);
         rp.reset(-1);
         rm.reset(-1);
-        for (int rb = r0; rb < r1; rb += PBATCH) {
+        for (int rb = w.r0; rb < w.r1; rb += PBATCH) {
             double ar[PBATCH], ai[PBATCH], br[PBATCH], bi[PBATCH];
 #pragma unroll
             for (int u = 0; u < PBATCH; u++) {
                 const int r = rb + u;
                 ar[u] = ai[u] = br[u] = bi[u] = 0;
-                if (r < r1 && lane_on) {
-                    const int i0 = r / ext[1], i1 = r - i0 * ext[1];
-                    CLoad<T>::get(a + (o[0] + i0) * g.sa[0] + (o[1] + i1) * g.sa[1] + offa2, ar[u], ai[u]);
-                    if (P.cross)
-                        CLoad<T>::get(b + (o[0] + i0) * g.sb[0] + (o[1] + i1) * g.sb[1] + offb2, br[u], bi[u]);
+                if (r < w.r1 && w.lane_on) {
+                    int i0, i1;
+                    row_index(t, r, i0, i1);
+                    CLoad<T>::get(row_ptr(a, t, g.sa, i0, i1, offa2), ar[u], ai[u]);
+                    if (P.cross) CLoad<T>::get(row_ptr(b, t, g.sb, i0, i1, offb2), br[u], bi[u]);
                 }
             }
 #pragma unroll
             for (int u = 0; u < PBATCH; u++) {
                 const int r = rb + u;
-                if (!(r < r1 && lane_on)) continue;
-                const int i0 = r / ext[1], i1 = r - i0 * ext[1];
-                const double km[3] = {kax[i0], kax[64 + i1], k2ax};
+                if (!(r < w.r1 && w.lane_on)) continue;
+                int i0, i1;
+                row_index(t, r, i0, i1);
                 double kk[3];
-                const double kmag = mode_k(g, km[0], km[1], km[2], kk);
+                const double kmag = mode_k(g, L.kax[i0], L.kax[64 + i1], k2ax, kk);
                 if (!(kmag >= wk0 && kmag < wk1)) continue;
-                const int j = find_bin(sed, nb, kmag, guess(kmag, ke0, kinv) - wlo);
+                const int j = window_bin(L.sed, nb, wlo, kmag, q);
                 double vr, vi;
                 if (P.cross) {
                     vr = ar[u] * br[u] + ai[u] * bi[u];
@@ -138,29 +88,13 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
                 }
                 vr *= P.volume;
                 vi *= P.volume;
-                if (P.deconv_pow) {
-                    const double sm3[3] = {sax[i0], sax[64 + i1], s2ax};
-#pragma unroll
-                    for (int d = 0; d < 3; d++) {
-                        const double sp = g.ax[0] == d ? sm3[0] : (g.ax[1] == d ? sm3[1] : sm3[2]);
-                        vr /= sp;
-                        vi /= sp;
-                    }
-                }
-                bool h = false;
-                if (P.hermitian) {
-                    const int64_t il = g.alast == 2 ? ilast_fixed
-                                                    : g.start[g.alast] + o[g.alast] + (g.alast == 0 ? i0 : i1);
-                    h = il != 0 && il != g.nlast / 2;
-                }
+                if (P.deconv_pow) sinc_divide(g, L.sax[i0], L.sax[64 + i1], s2ax, vr, vi);
+                const bool h = mode_hermitian(P, g, t, ilast_fixed, i0, i1);
                 double mu = 0;
                 if (MU || POLES) mu = mode_mu(g, kk, kmag);
 
                 // 1-d table: the mode and (h) its conjugate at -mu
-                if (j != r1d.key) {
-                    r1d.flush(t1, s1, s1);
-                    r1d.reset(j);
-                }
+                r1d.select(j, L.t1, s1);
                 r1d.s[0] += h ? 2.0 : 1.0;
                 r1d.s[1] += h ? 2.0 * kmag : kmag;
                 r1d.s[2] += h ? 2.0 * vr : vr;
@@ -178,10 +112,10 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
                     }
                 }
                 if (MU) {
-                    const int mp = mu_bin(smu, nmu, mu, minv);
+                    const int mp = mu_bin(L.smu, nmu, mu, q.minv);
                     const int cp = mp < 0 ? -1 : j * nmu + mp;
                     if (cp >= 0) {
-                        if (cp != rp.key) { rp.flush(t2, 5, 5); rp.reset(cp); }
+                        rp.select(cp, L.t2, 5);
                         rp.s[0] += 1.0;
                         rp.s[1] += kmag;
                         rp.s[2] += mu;
@@ -189,10 +123,10 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
                         rp.s[4] += vi;
                     }
                     if (h) {
-                        const int mm = mu_bin(smu, nmu, -mu, minv);
+                        const int mm = mu_bin(L.smu, nmu, -mu, q.minv);
                         const int cm = mm < 0 ? -1 : j * nmu + mm;
                         if (cm >= 0) {
-                            if (cm != rm.key) { rm.flush(t2, 5, 5); rm.reset(cm); }
+                            rm.select(cm, L.t2, 5);
                             rm.s[0] += 1.0;
                             rm.s[1] += kmag;
                             rm.s[2] += -mu;
@@ -203,21 +137,14 @@ __global__ void __launch_bounds__(PBLOCK) power_kernel(PParams P, PGeom g, const
                 }
             }
         }
-        r1d.flush(t1, s1, s1);
+        r1d.flush(L.t1, s1, s1);
         if (MU) {
-            rp.flush(t2, 5, 5);
-            rm.flush(t2, 5, 5);
+            rp.flush(L.t2, 5, 5);
+            rm.flush(L.t2, 5, 5);
         }
         __syncthreads();
-        // the window into the global sums: contiguous runs of doubles, bins that received nothing skipped
-        double *g1 = acc + (int64_t)wlo * s1;
-        for (int i = tid; i < nb * s1; i += PBLOCK)
-            if (t1[(i / s1) * s1] != 0) unsafeAtomicAdd(g1 + i, t1[i]);
-        if (MU) {
-            double *g2 = acc + (int64_t)P.nk * s1 + (int64_t)wlo * nmu * 5;
-            for (int i = tid; i < nb * nmu * 5; i += PBLOCK)
-                if (t2[(i / 5) * 5] != 0) unsafeAtomicAdd(g2 + i, t2[i]);
-        }
+        window_add(acc + (int64_t)wlo * s1, L.t1, nb * s1, s1);
+        if (MU) window_add(acc + (int64_t)P.nk * s1 + (int64_t)wlo * nmu * 5, L.t2, nb * nmu * 5, 5);
         __syncthreads();
     }
 }
@@ -240,17 +167,8 @@ extern "C" int pmx_power_project(const pmx_power *p, int32_t ndim, int32_t elsiz
     const int rc = power_setup(p, ndim, elsize, a, a_strides, b, b_strides, shape, start, nmesh, boxsize, kedges,
                                muedges, 4 + 2 * (p ? p->npoles : 0), 5, P, g, &ntiles, &lds);
     if (rc != PMX_OK || ntiles == 0) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)ntiles);
-    const bool mu = p->nmu > 0, poles = p->npoles > 0;
-    with_canvas(elsize, [&](auto c) {
-        using T = typename decltype(c)::type;
-        with_bool(mu, [&](auto m) {
-            with_bool(poles, [&](auto pl) {
-                power_kernel<T, m, pl><<<grid, PBLOCK, lds, s>>>(P, g, (const char *)a, (const char *)b, kedges, muedges, acc);
-            });
-        });
-    });
-    PMX_HIP_CHECK(hipGetLastError());
-    return PMX_OK;
+    return launch_tiles(
+        elsize, p, ntiles, lds, stream,
+        [](auto c, auto m, auto pl) { return power_kernel<typename decltype(c)::type, m, pl>; }, P, g, (const char *)a,
+        (const char *)b, kedges, muedges, acc);
 }

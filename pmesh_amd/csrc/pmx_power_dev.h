@@ -1,9 +1,17 @@
-// pmx_power_dev.h — what the binned power spectrum (pmx_power.hip) and its adjoint (pmx_power_grad.hip) share, so that
-// both land every mode in the same bin: the tile geometry, the per-axis wavenumber and sinc tables of a tile with the
-// extreme |k_d| of its index box, the window search over the k edges, find_bin / guess / mu_bin, the Legendre
-// recurrence, and the host side that orders the axes and sizes the LDS window.  The wavenumber (k_divided), the sinc
-// power, the complex loads and the axis-order rule come from pmx_block_dev.h.  The arithmetic is the forward's,
-// statement for statement (-ffp-contract=off keeps its roundings).
+// pmx_power_dev.h — the tile walk of the binned two-point statistics: what power_kernel (pmx_power.hip), its adjoint
+// power_vjp_kernel (pmx_power_grad.hip) and corr_kernel / corr_vjp_kernel (pmx_corr.hip) share, so that every mode
+// (cell) lands in the bin the forward put it in.  In reading order: the tile geometry and parameters; find_bin / guess /
+// mu_bin;
+// the per-axis tables of a tile on the k side (tile_axis) and the real side (tile_axis_real) with the extreme |k_d| of
+// its index box; mode_k / mode_mu / the Legendre recurrence; then the skeleton every tile kernel is written in — the
+// LDS layout next to the host formula that sizes it (PLds, lds_layout, lds_window, lds_doubles), the tile prologue
+// (tile_begin), the row split (wave_rows, row_index, row_ptr), the window loop (window_edges, window_zero, window_load,
+// window_bin, window_add), the running sums of the forwards (Run), the adjoints' rule for who writes an element
+// (pass_writes_zero, tile_zero), the Hermitian weight and the sinc division of the k side (mode_hermitian,
+// sinc_divide) — and the host side: power_setup, which orders the axes and sizes the window, and launch_tiles, the
+// <T, MU, POLES> dispatch.  The wavenumber (k_divided), the sinc power, the complex loads and the axis-order rule come
+// from pmx_block_dev.h.  The arithmetic is the forward's, statement for statement (-ffp-contract=off keeps its
+// roundings).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -186,6 +194,248 @@ __device__ __forceinline__ void tile_axis_real(const PGeom &g, int ax, int lane,
     if (lane == 0) { ext2[0] = mn; ext2[1] = mx; }
 }
 
+// ---- the skeleton of a tile kernel ---------------------------------------------------------------------------------
+
+// The dynamic LDS block of a workgroup, in doubles: two per-axis tables of the tile (the real side leaves the second
+// one unused), the mu edges, the k edges of the window, and the window of the bin table (s1 doubles per k bin) and of
+// the cell table (per_cell doubles per (k, mu) cell).  lds_layout carves what lds_window / lds_doubles size.
+struct PLds {
+    double *kax, *sax;                        // [3][64] each: k_d (r_d) and sinc(w_d/2)^deconv_pow along each axis
+    double *smu, *sed;                        // nmu + 1 mu edges (with MU), window + 1 k edges
+    double *t1, *t2;                          // window * s1, window * nmu * per_cell
+};
+
+constexpr int lds_fixed(int nmu) { return 2 * PAXIS + (nmu ? nmu + 1 : 0) + 1; }
+constexpr int lds_window(int nmu, int s1, int per_cell)
+{
+    return (PLDS_BUDGET - lds_fixed(nmu)) / (s1 + 1 + per_cell * nmu);
+}
+constexpr size_t lds_doubles(int nmu, int s1, int per_cell, int window)
+{
+    return (size_t)(lds_fixed(nmu) + window * (s1 + per_cell * nmu) + window);
+}
+
+template <bool MU> __device__ __forceinline__ PLds lds_layout(double *sm, const PParams &P)
+{
+    PLds L;
+    L.kax = sm;
+    L.sax = sm + PAXIS;
+    L.smu = sm + 2 * PAXIS;
+    L.sed = L.smu + (MU ? P.nmu + 1 : 0);
+    L.t1 = L.sed + P.window + 1;
+    L.t2 = L.t1 + P.window * P.s1;
+    return L;
+}
+
+// the tile of this workgroup: its origin and ragged extents along the memory-order axes, and the k bins blo .. bhi it
+// can touch (none: bhi < blo)
+struct PTile {
+    int64_t o[3];
+    int ext[3];
+    int blo, bhi;
+};
+
+// What every tile kernel begins with: the tile of blockIdx.x, its per-axis tables (waves 0, 1, 2: one axis each; REAL:
+// separations, else wavenumbers and sinc powers), the mu edges (wave 3) and its range of bins.
+template <bool REAL, bool MU>
+__device__ __forceinline__ PTile tile_begin(const PParams &P, const PGeom &g, const PLds &L, const double *edges,
+                                            const double *muedges)
+{
+    __shared__ double s_ext[3][2];
+    __shared__ int s_range[2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    PTile t;
+    int64_t tile = blockIdx.x;
+    const int c2 = (int)(tile % g.nt[2]);
+    tile /= g.nt[2];
+    const int c1 = (int)(tile % g.nt[1]), c0 = (int)(tile / g.nt[1]);
+    t.o[0] = (int64_t)c0 * PT0;
+    t.o[1] = (int64_t)c1 * PT1;
+    t.o[2] = (int64_t)c2 * PT2;
+    t.ext[0] = (int)min((int64_t)PT0, g.shape[0] - t.o[0]);
+    t.ext[1] = (int)min((int64_t)PT1, g.shape[1] - t.o[1]);
+    t.ext[2] = (int)min((int64_t)PT2, g.shape[2] - t.o[2]);
+    // (selects, not t.ext[wv]: an index that is not a constant would put the tile into scratch memory)
+    if (wv < 3) {
+        const int e = wv == 0 ? t.ext[0] : (wv == 1 ? t.ext[1] : t.ext[2]);
+        const int64_t o = wv == 0 ? t.o[0] : (wv == 1 ? t.o[1] : t.o[2]);
+        if (REAL) tile_axis_real(g, wv, lane, e, o, L.kax, s_ext[wv]);
+        else tile_axis(P, g, wv, lane, e, o, L.kax, L.sax, s_ext[wv]);
+    } else if (MU) {
+        for (int i = lane; i <= P.nmu; i += 64) L.smu[i] = muedges[i];
+    }
+    __syncthreads();
+    if (wv < 2) {
+        const int j = tile_bin_range(P, g, wv, lane, s_ext, edges);
+        if (lane == 0) s_range[wv] = j;
+    }
+    __syncthreads();
+    t.blo = s_range[0];
+    t.bhi = s_range[1];
+    return t;
+}
+
+// the rows r0 .. r1 - 1 of the tile this wave walks (row r = i0 * ext[1] + i1, a quarter of them per wave), and
+// whether this lane holds an element of each
+struct PRows {
+    int r0, r1;
+    bool lane_on;
+};
+
+__device__ __forceinline__ PRows wave_rows(const PTile &t)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nrows = t.ext[0] * t.ext[1], rper = (nrows + 3) / 4;
+    PRows w;
+    w.r0 = wv * rper;
+    w.r1 = min(nrows, w.r0 + rper);
+    w.lane_on = lane < t.ext[2];
+    return w;
+}
+
+__device__ __forceinline__ void row_index(const PTile &t, int r, int &i0, int &i1)
+{
+    i0 = r / t.ext[1];
+    i1 = r - i0 * t.ext[1];
+}
+
+// this lane's element of row (i0, i1) in a field at `base` of byte strides s (memory order); off2 = lane_off(t, s), the
+// part that no row changes.  (The sum stays a chain from `base`, as the kernels wrote it: summed apart and added to the
+// pointer at the end it cost power_vjp_kernel<MU, POLES> five registers and a wave per SIMD.)
+__device__ __forceinline__ int64_t lane_off(const PTile &t, const int64_t *s)
+{
+    return (t.o[2] + (threadIdx.x & 63)) * s[2];
+}
+template <typename C>
+__device__ __forceinline__ C *row_ptr(C *base, const PTile &t, const int64_t *s, int i0, int i1, int64_t off2)
+{
+    return base + (t.o[0] + i0) * s[0] + (t.o[1] + i1) * s[1] + off2;
+}
+
+// the guesses of the uniform edges: find_bin's first try among the k edges, mu_bin's among the mu edges
+struct PGuess {
+    double e0, inv, minv;
+};
+
+template <bool MU>
+__device__ __forceinline__ PGuess bin_guess(const PParams &P, const PLds &L, const double *edges)
+{
+    PGuess q;
+    q.e0 = edges[0];
+    q.inv = P.nk / (edges[P.nk] - edges[0]);
+    q.minv = MU ? P.nmu / (L.smu[P.nmu] - L.smu[0]) : 0;
+    return q;
+}
+
+// One pass of a tile covers the nb <= P.window bins from wlo on: their edges into sed, their tables zeroed (the
+// forwards' sums) or loaded from src (the adjoints' coefficients); a __syncthreads() follows in the kernel.
+__device__ __forceinline__ int window_edges(const PParams &P, const PTile &t, int wlo, double *sed, const double *edges)
+{
+    const int nb = min(P.window, t.bhi - wlo + 1);
+    for (int i = threadIdx.x; i <= nb; i += PBLOCK) sed[i] = edges[wlo + i];
+    return nb;
+}
+
+__device__ __forceinline__ void window_zero(double *tab, int n)
+{
+    for (int i = threadIdx.x; i < n; i += PBLOCK) tab[i] = 0;
+}
+__device__ __forceinline__ void window_load(double *tab, int n, const double *src)
+{
+    for (int i = threadIdx.x; i < n; i += PBLOCK) tab[i] = src[i];
+}
+
+// the bin of x, window edges sed[0] <= x < sed[nb], counted from wlo
+__device__ __forceinline__ int window_bin(const double *sed, int nb, int wlo, double x, const PGuess &q)
+{
+    return find_bin(sed, nb, x, guess(x, q.e0, q.inv) - wlo);
+}
+
+// the window table tab (n doubles in records of `width`, the count first) into the global sums: contiguous runs of
+// doubles, bins that received nothing skipped
+__device__ __forceinline__ void window_add(double *sums, const double *tab, int n, int width)
+{
+    for (int i = threadIdx.x; i < n; i += PBLOCK)
+        if (tab[(i / width) * width] != 0) unsafeAtomicAdd(sums + i, tab[i]);
+}
+
+// the running sums of one thread for one key (a bin, or a (bin, mu) cell): the LDS atomics of the forwards happen
+// once per run of modes with the same key, not once per mode
+template <int N> struct Run {
+    int key;
+    double s[N];
+    __device__ __forceinline__ void reset(int k)
+    {
+        key = k;
+#pragma unroll
+        for (int i = 0; i < N; i++) s[i] = 0;
+    }
+    __device__ __forceinline__ void flush(double *tab, int stride, int n)
+    {
+        if (key < 0) return;
+        double *t = tab + key * stride;
+#pragma unroll
+        for (int i = 0; i < N; i++)
+            if (i < n) atomicAdd(t + i, s[i]);
+    }
+    // the run of `k`: the sums so far go to tab when the key changes
+    __device__ __forceinline__ void select(int k, double *tab, int stride)
+    {
+        if (k != key) {
+            flush(tab, stride, stride);
+            reset(k);
+        }
+    }
+};
+
+// The adjoints write every element of a tile exactly once.  A tile that spans more bins than a window holds takes one
+// pass per window: the pass whose window holds an element's bin writes it, and an element x with no bin at all (outside
+// [lo, hi), the edges all passes cover together) is written, as zero, by the first pass.  (corr_vjp_kernel spells
+// the same test out: through this function its (r, mu) variant ran 0.8 % slower at 512^3, 1.227 against 1.217 ms.)
+__device__ __forceinline__ bool pass_writes_zero(bool first, double x, double lo, double hi)
+{
+    return first && !(x >= lo && x < hi);
+}
+
+// a tile none of whose elements has a bin: put(i0, i1) stores this lane's zero of every row of this wave
+template <typename Put> __device__ __forceinline__ void tile_zero(const PTile &t, const PRows &w, Put put)
+{
+    if (!w.lane_on) return;
+    for (int r = w.r0; r < w.r1; r++) {
+        int i0, i1;
+        row_index(t, r, i0, i1);
+        put(i0, i1);
+    }
+}
+
+// ---- the k side alone (power_kernel and power_vjp_kernel) -----------------------------------------------------------
+
+// A mode of a compressed spectrum stands for itself and its conjugate when its index along the logical last axis is
+// neither 0 nor N / 2.  ilast_fixed: that index where the last axis is the lane's (g.alast == 2).
+__device__ __forceinline__ bool mode_hermitian(const PParams &P, const PGeom &g, const PTile &t, int64_t ilast_fixed,
+                                               int i0, int i1)
+{
+    bool h = false;
+    if (P.hermitian) {
+        // (selects, as in tile_begin: t.o[g.alast] would put the tile into scratch memory)
+        const int64_t il = g.alast == 2 ? ilast_fixed
+                                        : g.start[g.alast] + (g.alast == 0 ? t.o[0] : t.o[1]) + (g.alast == 0 ? i0 : i1);
+        h = il != 0 && il != g.nlast / 2;
+    }
+    return h;
+}
+
+// vr, vi over the sinc powers of the mode (s0, s1, s2 in memory order), divided axis by axis in logical order
+__device__ __forceinline__ void sinc_divide(const PGeom &g, double s0, double s1, double s2, double &vr, double &vi)
+{
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const double sp = g.ax[0] == d ? s0 : (g.ax[1] == d ? s1 : s2);
+        vr /= sp;
+        vi /= sp;
+    }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------
 
 // Checks the arguments the forward and the adjoint share and fills the kernel parameters: per_bin / per_cell doubles
@@ -219,8 +469,7 @@ static int power_setup(const pmx_power *p, int32_t ndim, int32_t elsize, const v
     P.cross = b ? 1 : 0;
     P.volume = p->volume;
     P.s1 = per_bin;
-    const int fixed = 2 * PAXIS + (p->nmu ? p->nmu + 1 : 0) + 1;
-    P.window = (PLDS_BUDGET - fixed) / (P.s1 + 1 + per_cell * p->nmu);
+    P.window = lds_window(p->nmu, per_bin, per_cell);
     PMX_REQUIRE(P.window >= 1, PMX_EUNSUPPORTED, "bin table does not fit");
 
     // memory order: axes of extent 1 slowest, then by decreasing stride of a
@@ -263,7 +512,24 @@ static int power_setup(const pmx_power *p, int32_t ndim, int32_t elsize, const v
         return PMX_OK;
     }
     PMX_REQUIRE(*ntiles < (1ll << 31), PMX_EUNSUPPORTED, "more than 2^31 tiles");
-    *lds = sizeof(double) * (size_t)(fixed + P.window * (P.s1 + per_cell * p->nmu) + P.window);
+    *lds = sizeof(double) * lds_doubles(p->nmu, per_bin, per_cell, P.window);
+    return PMX_OK;
+}
+
+// The launch of one of the tile kernels K<T, MU, POLES>: pick(c, m, pl) returns the instance for the canvas type, the
+// (k, mu) table and the multipoles; one workgroup per tile.
+template <typename Pick, typename... Args>
+static int launch_tiles(int32_t elsize, const pmx_power *p, int64_t ntiles, size_t lds, void *stream, Pick pick,
+                        Args... args)
+{
+    with_canvas(elsize, [&](auto c) {
+        with_bool(p->nmu > 0, [&](auto m) {
+            with_bool(p->npoles > 0, [&](auto pl) {
+                pick(c, m, pl)<<<dim3((unsigned)ntiles), PBLOCK, lds, (hipStream_t)stream>>>(args...);
+            });
+        });
+    });
+    PMX_HIP_CHECK(hipGetLastError());
     return PMX_OK;
 }
 

@@ -23,32 +23,45 @@ import torch
 from . import _abi, backend
 
 
-class PowerResult(object):
-    """The binned spectrum.  1-d bins (Nk): ``kedges``, ``k`` (mean |k|), ``modes`` (count), ``power`` (complex),
-    ``poles`` (dict ell -> complex array).  (k, mu) bins (Nk x Nmu), None without ``muedges``: ``muedges``, ``k2d``,
-    ``mu2d``, ``modes2d``, ``power2d``.  Means are weighted sums over the count; empty bins hold NaN."""
+class _Result(object):
+    """The binned statistic unpacked from the raw sums `acc` of the tile kernels: per bin ``[count, sum |x|, sum v,
+    sum v L_ell per pole]``, then per (bin, mu) cell ``[count, sum |x|, sum mu, sum v]``, every v of ``_width`` columns
+    ((re, im) pairs of the complex power, one real column of the correlation).  A subclass names |x| (``_x``: the
+    attributes x, xedges, x2d) and v (``_v``: v, v2d)."""
 
-    def __init__(self, kedges, muedges, acc, ells):
-        nk = len(kedges) - 1
-        s1 = 4 + 2 * len(ells)
-        a1 = acc[:nk * s1].reshape(nk, s1)
-        self.kedges = kedges
+    def __init__(self, edges, muedges, acc, ells):
+        w = self._width
+        nb = len(edges) - 1
+        s1 = 2 + w * (1 + len(ells))
+
+        def v(a, i):
+            return a[..., i] + 1j * a[..., i + 1] if w == 2 else a[..., i]
+        a1 = acc[:nb * s1].reshape(nb, s1)
+        setattr(self, self._x + 'edges', edges)
         self.muedges = muedges
         with numpy.errstate(invalid='ignore', divide='ignore'):
             n = a1[:, 0]
             self.modes = numpy.rint(n).astype('i8')
-            self.k = a1[:, 1] / n
-            self.power = (a1[:, 2] + 1j * a1[:, 3]) / n
-            self.poles = {ell: (2 * ell + 1) * (a1[:, 4 + 2 * p] + 1j * a1[:, 5 + 2 * p]) / n
-                          for p, ell in enumerate(ells)}
-            self.k2d = self.mu2d = self.modes2d = self.power2d = None
+            setattr(self, self._x, a1[:, 1] / n)
+            setattr(self, self._v, v(a1, 2) / n)
+            self.poles = {ell: (2 * ell + 1) * v(a1, 2 + w * (1 + p)) / n for p, ell in enumerate(ells)}
+            self.mu2d = self.modes2d = None
+            setattr(self, self._x + '2d', None)
+            setattr(self, self._v + '2d', None)
             if muedges is not None:
-                a2 = acc[nk * s1:].reshape(nk, len(muedges) - 1, 5)
+                a2 = acc[nb * s1:].reshape(nb, len(muedges) - 1, 3 + w)
                 n2 = a2[..., 0]
                 self.modes2d = numpy.rint(n2).astype('i8')
-                self.k2d = a2[..., 1] / n2
+                setattr(self, self._x + '2d', a2[..., 1] / n2)
                 self.mu2d = a2[..., 2] / n2
-                self.power2d = (a2[..., 3] + 1j * a2[..., 4]) / n2
+                setattr(self, self._v + '2d', v(a2, 3) / n2)
+
+
+class PowerResult(_Result):
+    """The binned spectrum.  1-d bins (Nk): ``kedges``, ``k`` (mean |k|), ``modes`` (count), ``power`` (complex),
+    ``poles`` (dict ell -> complex array).  (k, mu) bins (Nk x Nmu), None without ``muedges``: ``muedges``, ``k2d``,
+    ``mu2d``, ``modes2d``, ``power2d``.  Means are weighted sums over the count; empty bins hold NaN."""
+    _x, _v, _width = 'k', 'power', 2
 
 
 def _edges(name, edges, lo=None, hi=None):
@@ -71,95 +84,159 @@ def _complex(field):
     return field
 
 
-def _binning(ndim, name, edges, muedges, los, poles):
-    """the checked bin edges `name` (kedges; redges on the real side), mu edges (or None), multipole orders and unit
-    line of sight of a binned two-point statistic on a mesh of ndim dimensions"""
-    ke = _edges(name, edges)
-    if len(ke) - 1 > _abi.PMX_POWER_MAX_KBINS:
-        raise ValueError('%d %s bins: more than PMX_POWER_MAX_KBINS = %d'
-                         % (len(ke) - 1, name[0], _abi.PMX_POWER_MAX_KBINS))
-    me = None
-    if muedges is not None:
-        me = _edges('muedges', muedges, -1.0, 1.0)
-        if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
-            raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d'
-                             % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
-    ells = [int(ell) for ell in poles]
-    if len(ells) > _abi.PMX_POWER_MAX_POLES:
-        raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
-    if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
-        raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
-    if los is None:
-        los = numpy.zeros(ndim)
-        los[-1] = 1.0
-    los = numpy.array(los, dtype='f8').reshape(-1)
-    norm = numpy.sqrt((los ** 2).sum())
-    if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
-        raise ValueError('los must be a nonzero vector of %d components' % ndim)
-    return ke, me, ells, los / norm
+def _ndim(pm, what):
+    ndim = len(pm.Nmesh)
+    if ndim > _abi.PMX_MAXDIM:
+        raise NotImplementedError('%s of meshes of more than %d dimensions' % (what, _abi.PMX_MAXDIM))
+    return ndim
 
 
-class _Plan(object):
-    """the checked arguments of one spectrum: the fields, the edges, the multipole orders and the pmx_power struct"""
+class _Binning(object):
+    """The binning of one two-point statistic on a mesh of ndim dimensions, checked: the edges `name` (kedges; redges
+    on the real side) and mu edges (or None) on the host (``edges``, ``me``) and on the device (``et``, ``mt``), the
+    multipole orders ``ells``, the filled pmx_power struct ``p`` with the unit line of sight, and the widths of the
+    tables the kernels keep per bin and per (bin, mu) cell: ``s1``, ``s2`` doubles of sums and ``c1``, ``c2`` of
+    adjoint coefficients.  `result` is the _Result class of the statistic; comm: the ranks whose sums are added."""
 
-    def __init__(self, field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex):
-        a = convert(field)
-        pm = a.pm
-        ndim = len(pm.Nmesh)
-        if ndim > _abi.PMX_MAXDIM:
-            raise NotImplementedError('power spectra of meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
-        b = None
-        if other is not None:
-            b = convert(other)
-            if b.pm is not pm and (tuple(b.pm.Nmesh) != tuple(pm.Nmesh) or tuple(b.pm.BoxSize) != tuple(pm.BoxSize)
-                                   or b.pm.comm is not pm.comm):
-                raise ValueError('the two fields belong to different meshes')
-            _same_layout(a, b)
-        if a.value.dtype not in (torch.complex64, torch.complex128):
-            raise ValueError('power_spectrum measures complex64 or complex128 fields')
-
-        ke, me, ells, los = _binning(ndim, 'kedges', kedges, muedges, los, poles)
+    def __init__(self, ndim, name, edges, muedges, los, poles, result, hermitian=0, deconv_pow=0, volume=1.0, comm=None):
+        e = _edges(name, edges)
+        if len(e) - 1 > _abi.PMX_POWER_MAX_KBINS:
+            raise ValueError('%d %s bins: more than PMX_POWER_MAX_KBINS = %d'
+                             % (len(e) - 1, name[0], _abi.PMX_POWER_MAX_KBINS))
+        me = None
+        if muedges is not None:
+            me = _edges('muedges', muedges, -1.0, 1.0)
+            if len(me) - 1 > _abi.PMX_POWER_MAX_MUBINS:
+                raise ValueError('%d mu bins: more than PMX_POWER_MAX_MUBINS = %d'
+                                 % (len(me) - 1, _abi.PMX_POWER_MAX_MUBINS))
+        ells = [int(ell) for ell in poles]
+        if len(ells) > _abi.PMX_POWER_MAX_POLES:
+            raise ValueError('%d multipoles: more than PMX_POWER_MAX_POLES = %d' % (len(ells), _abi.PMX_POWER_MAX_POLES))
+        if len(set(ells)) != len(ells) or any(ell < 0 or ell > _abi.PMX_POWER_MAX_ELL for ell in ells):
+            raise ValueError('poles must be distinct orders in 0..PMX_POWER_MAX_ELL = %d' % _abi.PMX_POWER_MAX_ELL)
+        if los is None:
+            los = numpy.zeros(ndim)
+            los[-1] = 1.0
+        los = numpy.array(los, dtype='f8').reshape(-1)
+        norm = numpy.sqrt((los ** 2).sum())
+        if len(los) != ndim or not numpy.isfinite(norm) or norm == 0:
+            raise ValueError('los must be a nonzero vector of %d components' % ndim)
         if int(deconv_pow) != deconv_pow or deconv_pow < 0:
             raise ValueError('deconv_pow must be a non-negative integer')
 
         p = _abi.Power()
-        p.nk = len(ke) - 1
+        p.nk = len(e) - 1
         p.nmu = 0 if me is None else len(me) - 1
         p.npoles = len(ells)
         for i, ell in enumerate(ells):
             p.poles[i] = ell
-        p.hermitian = int(bool(a.compressed))
+        p.hermitian = int(hermitian)
         p.deconv_pow = int(deconv_pow)
-        p.volume = float(numpy.prod(pm.BoxSize))
+        p.volume = float(volume)
         for d in range(ndim):
-            p.los[d] = float(los[d])
+            p.los[d] = float(los[d] / norm)
 
-        self.a, self.b, self.pm, self.p, self.ke, self.me, self.ells = a, b, pm, p, ke, me, ells
-        self.s1 = 4 + 2 * len(ells)
-        be = backend.get()
-        self.kt = torch.from_numpy(ke).to(be.device)
-        self.mt = torch.from_numpy(me).to(be.device) if me is not None else None
+        self.p, self.edges, self.me, self.ells, self.result, self.comm = p, e, me, ells, result, comm
+        w = result._width
+        self.c1, self.c2 = w * (1 + len(ells)), w
+        self.s1, self.s2 = 2 + self.c1, 3 + self.c2
+        dev = backend.get().device
+        self.et = torch.from_numpy(e).to(dev)
+        self.mt = torch.from_numpy(me).to(dev) if me is not None else None
 
-    def sums(self, a, b):
-        """the raw sums of pmx_power_project for the fields a and b (None: a) of this plan's layout, summed over the
-        ranks: a host vector"""
-        be = backend.get()
+    def zeros(self):
+        """the accumulator of the forward kernels, on the device"""
         p = self.p
-        acc = torch.zeros(p.nk * self.s1 + p.nk * p.nmu * 5, dtype=torch.float64, device=be.device)
-        try:
-            be.power_project(p, a.value, b.value if b is not None else None, a.start, self.pm.Nmesh, self.pm.BoxSize,
-                             self.kt, self.mt, acc)
-        except backend.PmxError as e:
-            if e.code == _abi.PMX_EUNSUPPORTED:
-                raise ValueError(str(e))
-            raise
+        return torch.zeros(p.nk * self.s1 + p.nk * p.nmu * self.s2, dtype=torch.float64, device=backend.get().device)
+
+    def unpack(self, acc):
+        return self.result(self.edges, self.me, acc, self.ells)
+
+    def sums(self, call):
+        """the raw sums `call(acc)` adds into a zeroed accumulator, summed over the ranks: a host vector"""
+        acc = self.zeros()
+        _unsupported_is_value_error(call, acc)
         # one sum over the ranks of the raw sums, then the division
-        if self.pm.comm.size > 1:
-            acc = self.pm.comm.allreduce(acc)
+        if self.comm is not None and self.comm.size > 1:
+            acc = self.comm.allreduce(acc)
         return acc.cpu().numpy()
 
-    def result(self, acc):
-        return PowerResult(self.ke, self.me, acc, self.ells)
+    def coefficients(self, v, v_poles, v2d, result, forward, real=False):
+        """The coefficient table of the adjoint kernels on the device, in acc's layout without the count, |x| and mu
+        columns: v / count per bin, (2l + 1) v_poles[l] / count per pole, v2d / count per cell, zero in empty bins.
+        The cotangents are named after the statistic (v_power, v_corr2d); real: they must be.  result: the forward's
+        _Result for its counts, or None for the one `forward()` returns."""
+        nb, nmu, ells, name = self.p.nk, self.p.nmu, self.ells, self.result._v
+
+        def cotangent(what, x, shape):
+            x = _cotangent(what, x, shape)
+            if real and (x.imag != 0).any():
+                raise ValueError('%s must be real: the correlation function is' % what)
+            return x.real if real else x
+        if v2d is not None and self.me is None:
+            raise ValueError('v_%s2d needs muedges' % name)
+        v_poles = dict(v_poles) if v_poles else {}
+        unknown = [ell for ell in v_poles if ell not in ells]
+        if unknown:
+            raise ValueError('v_poles has orders %s that are not among poles %s' % (unknown, ells))
+        cols = [cotangent('v_' + name, v, (nb,))]
+        cols += [(2 * ell + 1) * cotangent('v_poles[%d]' % ell, v_poles.get(ell), (nb,)) for ell in ells]
+        v2 = cotangent('v_%s2d' % name, v2d, (nb, nmu)) if nmu else None
+
+        if result is None:
+            result = forward()
+        elif tuple(result.modes.shape) != (nb,) or (nmu > 0) != (result.modes2d is not None) or \
+                (nmu and tuple(result.modes2d.shape) != (nb, nmu)):
+            raise ValueError('result is not the %s of these arguments' % self.result.__name__)
+
+        def table(x, count):
+            x = x * numpy.where(count > 0, 1.0 / numpy.maximum(count, 1), 0.0)
+            return x.real if real else numpy.stack([x.real, x.imag], axis=-1)
+        coef = numpy.concatenate([numpy.stack([table(c, result.modes) for c in cols], axis=1).reshape(-1)]
+                                 + ([table(v2, result.modes2d).reshape(-1)] if nmu else []))
+        return torch.from_numpy(coef).to(backend.get().device)
+
+
+def _unsupported_is_value_error(call, *args):
+    """call(*args); what the native library does not support is the caller's ValueError"""
+    try:
+        return call(*args)
+    except backend.PmxError as e:
+        if e.code == _abi.PMX_EUNSUPPORTED:
+            raise ValueError(str(e))
+        raise
+
+
+class _Plan(_Binning):
+    """the checked arguments of one spectrum: the fields (a, b or None) and their binning"""
+
+    def __init__(self, field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex):
+        a = convert(field)
+        pm = a.pm
+        ndim = _ndim(pm, 'power spectra')
+        b = None
+        if other is not None:
+            b = convert(other)
+            _same_mesh(a, b)
+            _same_layout(a, b)
+        if a.value.dtype not in (torch.complex64, torch.complex128):
+            raise ValueError('power_spectrum measures complex64 or complex128 fields')
+        _Binning.__init__(self, ndim, 'kedges', kedges, muedges, los, poles, PowerResult, bool(a.compressed), deconv_pow,
+                          numpy.prod(pm.BoxSize), pm.comm)
+        self.a, self.b, self.pm = a, b, pm
+
+    def sums(self, a, b):
+        """the raw sums of pmx_power_project for the fields a and b (None: a) of this plan's layout"""
+        return _Binning.sums(self, lambda acc: backend.get().power_project(
+            self.p, a.value, b.value if b is not None else None, a.start, self.pm.Nmesh, self.pm.BoxSize, self.et,
+            self.mt, acc))
+
+
+
+def _same_mesh(a, b):
+    if b.pm is not a.pm and (tuple(b.pm.Nmesh) != tuple(a.pm.Nmesh) or tuple(b.pm.BoxSize) != tuple(a.pm.BoxSize)
+                             or b.pm.comm is not a.pm.comm):
+        raise ValueError('the two fields belong to different meshes')
 
 
 def _same_layout(a, b):
@@ -181,7 +258,7 @@ def power_spectrum(field, kedges, other=None, muedges=None, los=None, poles=(), 
     deconv_pow : divide v by prod_d sinc(w_d / 2)^deconv_pow (window compensation).
     """
     plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow)
-    return plan.result(plan.sums(plan.a, plan.b))
+    return plan.unpack(plan.sums(plan.a, plan.b))
 
 
 # ---- gradients -----------------------------------------------------------------------------------------------------
@@ -223,54 +300,40 @@ def power_spectrum_vjp(field, kedges, v_power=None, v_poles=None, v_power2d=None
     and of RealField.c2r_vjp before decompress_vjp: ``Re(u.cdot(grad))`` is the derivative of L along u.
     """
     plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex_only)
-    p, nk, nmu, ells = plan.p, plan.p.nk, plan.p.nmu, plan.ells
-    if v_power2d is not None and plan.me is None:
-        raise ValueError('v_power2d needs muedges')
-    v_poles = dict(v_poles) if v_poles else {}
-    unknown = [ell for ell in v_poles if ell not in ells]
-    if unknown:
-        raise ValueError('v_poles has orders %s that are not among poles %s' % (unknown, ells))
-    v1 = _cotangent('v_power', v_power, (nk,))
-    vp = [_cotangent('v_poles[%d]' % ell, v_poles.get(ell), (nk,)) for ell in ells]
-    v2 = _cotangent('v_power2d', v_power2d, (nk, nmu)) if nmu else None
-
-    if result is None:
-        result = plan.result(plan.sums(plan.a, plan.b))
-    elif tuple(result.modes.shape) != (nk,) or (nmu > 0) != (result.modes2d is not None) or \
-            (nmu and tuple(result.modes2d.shape) != (nk, nmu)):
-        raise ValueError('result is not the PowerResult of these arguments')
-
-    # the coefficient table: acc's layout without the count, |k| and mu columns
-    sc = 2 + 2 * len(ells)
-    coef = numpy.zeros(nk * sc + nk * nmu * 2)
-    c1 = coef[:nk * sc].reshape(nk, sc)
-    with numpy.errstate(invalid='ignore', divide='ignore'):
-        inv = numpy.where(result.modes > 0, 1.0 / result.modes, 0.0)
-        cols = [v1 * inv] + [(2 * ell + 1) * v * inv for ell, v in zip(ells, vp)]
-        for i, c in enumerate(cols):
-            c1[:, 2 * i], c1[:, 2 * i + 1] = c.real, c.imag
-        if nmu:
-            inv2 = numpy.where(result.modes2d > 0, 1.0 / result.modes2d, 0.0)
-            c2 = coef[nk * sc:].reshape(nk, nmu, 2)
-            c2[..., 0], c2[..., 1] = (v2 * inv2).real, (v2 * inv2).imag
-
-    be = backend.get()
     a, b, pm = plan.a, plan.b, plan.pm
-    # (the kernel writes every mode of the block: only the GPU backend hands out raw memory)
-    from .pm import _blank
-
-    def new(f):
-        return _blank(type(f), pm) if be.name == 'hip' and f.value.numel() else pm.create(type=type(f))
-    ga = new(a)
-    gb = new(b) if b is not None else None
-    try:
-        be.power_vjp(p, a.value, b.value if b is not None else None, ga.value, gb.value if gb is not None else None,
-                     a.start, pm.Nmesh, pm.BoxSize, plan.kt, plan.mt, torch.from_numpy(coef).to(be.device))
-    except backend.PmxError as e:
-        if e.code == _abi.PMX_EUNSUPPORTED:
-            raise ValueError(str(e))
-        raise
+    coef = plan.coefficients(v_power, v_poles, v_power2d, result, lambda: plan.unpack(plan.sums(a, b)))
+    ga = _blank_like(a)
+    gb = _blank_like(b) if b is not None else None
+    _unsupported_is_value_error(backend.get().power_vjp, plan.p, a.value, b.value if b is not None else None, ga.value,
+                                gb.value if gb is not None else None, a.start, pm.Nmesh, pm.BoxSize, plan.et, plan.mt,
+                                coef)
     return ga if b is None else (ga, gb)
+
+
+def _blank_like(f, cls=None):
+    """a new field of f's mesh, of f's type or of `cls`; raw memory on the device, where the kernels write every
+    element of it (only the GPU backend hands out raw memory)"""
+    from .pm import _blank, _typestr_to_type
+    cls = _typestr_to_type(cls) if cls is not None else type(f)
+    return _blank(cls, f.pm) if backend.get().name == 'hip' and f.value.numel() else f.pm.create(type=cls)
+
+
+def _jvp_terms(a, b, v_field, v_other, check):
+    """The pairs (x, y) whose bilinear statistics add up to the tangent of the statistic of (a, b or a) along v_field
+    (and v_other), each checked by `check` and against a's layout: (da, b), (a, db) and, for the auto statistic, the
+    second half (a, da).  Empty without tangents: the caller measures the forward's counts alone."""
+    if v_other is not None and b is None:
+        raise ValueError('v_other needs other')
+    terms = []
+    for v, first in ((v_field, True), (v_other, False)):
+        if v is None:
+            continue
+        v = check(v)
+        _same_layout(a, v)
+        terms.append((v, b if b is not None else a) if first else (a, v))
+    if b is None and terms:
+        terms.append((a, terms[0][0]))
+    return terms
 
 
 def power_spectrum_jvp(field, kedges, v_field=None, v_other=None, other=None, muedges=None, los=None, poles=(),
@@ -283,19 +346,7 @@ def power_spectrum_jvp(field, kedges, v_field=None, v_other=None, other=None, mu
     v_field, v_other : ComplexField objects of the fields' layout; None counts as zero."""
     plan = _Plan(field, kedges, other, muedges, los, poles, deconv_pow, convert=_complex_only)
     a, b = plan.a, plan.b
-    if v_other is not None and b is None:
-        raise ValueError('v_other needs other')
-    terms = []
-    for v, partner, first in ((v_field, b if b is not None else a, True), (v_other, a, False)):
-        if v is None:
-            continue
-        v = _complex_only(v)
-        _same_layout(a, v)
-        terms.append((v, partner) if first else (partner, v))
-    if b is None and terms:
-        terms.append((a, terms[0][0]))                       # acc(a, da): the second half of the auto tangent
-    if not terms:
-        terms = [(a, b)]                                     # for the counts alone
+    terms = _jvp_terms(a, b, v_field, v_other, _complex_only) or [(a, b)]    # (a, b): for the counts alone
     accs = [plan.sums(x, y) for x, y in terms]
     acc = sum(accs)
     # counts, |k| and mu sums are the same in every term: the forward's
@@ -309,4 +360,4 @@ def power_spectrum_jvp(field, kedges, v_field=None, v_other=None, other=None, mu
         t1[:, 2:] = 0
         if nmu:
             t2[..., 3:] = 0
-    return plan.result(acc)
+    return plan.unpack(acc)

@@ -26,10 +26,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from pmesh_amd import _abi, backend  # noqa: E402
-from pmesh_amd.correlation import correlation_function  # noqa: E402
+from pmesh_amd import backend  # noqa: E402
+from pmesh_amd.correlation import CorrResult, correlation_function  # noqa: E402
 from pmesh_amd.pm import ParticleMesh  # noqa: E402
-from pmesh_amd.power import power_spectrum  # noqa: E402
+from pmesh_amd.power import PowerResult, _Binning, power_spectrum  # noqa: E402
 
 
 def timed(fn, reps):
@@ -44,19 +44,6 @@ def timed(fn, reps):
         b.synchronize()
         ts.append(a.elapsed_time(b))
     return float(numpy.median(ts))
-
-
-def params(nbins, me, poles, ndim, hermitian, volume):
-    p = _abi.Power()
-    p.nk = nbins
-    p.nmu = 0 if me is None else len(me) - 1
-    p.npoles = len(poles)
-    for i, ell in enumerate(poles):
-        p.poles[i] = ell
-    p.hermitian = hermitian
-    p.volume = volume
-    p.los[ndim - 1] = 1.0
-    return p
 
 
 def main():
@@ -82,15 +69,13 @@ def main():
             H, kf = L / N, 2 * numpy.pi / L
             re, ke = numpy.arange(N // 2 + 1) * H, numpy.arange(N // 2 + 1) * kf
             me = numpy.linspace(-1, 1, 11)
-            rt, kt, mt = (torch.from_numpy(e).to(be.device) for e in (re, ke, me))
             for name, mue, poles in (('plain', None, ()), ('poles', None, (0, 2, 4)), ('mu10', me, (0, 2, 4))):
-                m = mt if mue is not None else None
-                pc = params(len(re) - 1, mue, poles, 3, 0, 1.0)
-                pp = params(len(ke) - 1, mue, poles, 3, 1, L ** 3)
-                accc = torch.zeros(pc.nk * (3 + len(poles)) + pc.nk * pc.nmu * 4, dtype=torch.float64, device=be.device)
-                accp = torch.zeros(pp.nk * (4 + 2 * len(poles)) + pp.nk * pp.nmu * 5, dtype=torch.float64,
-                                   device=be.device)
-                coef = torch.rand(pc.nk * (1 + len(poles)) + pc.nk * pc.nmu, dtype=torch.float64, device=be.device)
+                # the package's own structs, edges and table widths: the real side, and the k side of the same options
+                bc = _Binning(3, 'redges', re, mue, None, poles, CorrResult)
+                bp = _Binning(3, 'kedges', ke, mue, None, poles, PowerResult, hermitian=1, volume=L ** 3)
+                pc, pp, rt, kt, m = bc.p, bp.p, bc.et, bp.et, bc.mt
+                accc, accp = bc.zeros(), bp.zeros()
+                coef = torch.rand(pc.nk * bc.c1 + pc.nk * pc.nmu * bc.c2, dtype=torch.float64, device=be.device)
                 tc = timed(lambda: be.corr_project(pc, f.value, f.start, pm.Nmesh, pm.BoxSize, rt, m, accc), args.reps)
                 tv = timed(lambda: be.corr_vjp(pc, g.value, g.start, pm.Nmesh, pm.BoxSize, rt, m, coef), args.reps)
                 tp = timed(lambda: be.power_project(pp, c.value, None, c.start, pm.Nmesh, pm.BoxSize, kt, m, accp),

@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from pmesh_amd import _abi, backend  # noqa: E402
+from pmesh_amd.power import PowerResult, _Binning  # noqa: E402
 
 # (name, shape, Nmesh, start, memory order of the input, of the outputs); memory order: logical axes, slowest first
 CASES = [
@@ -161,32 +162,27 @@ def run_case(be, name, shape, nmesh, start, oin, oout, cdt):
 
     # power spectrum and its adjoint
     nk, nmu = 6, 4
-    ke = torch.from_numpy(numpy.linspace(0, 1.2 * kny, nk + 1)).to(dev)
-    me = torch.from_numpy(numpy.linspace(-1, 1, nmu + 1)).to(dev)
     for form, mu, poles, cross, dp in (('1d-auto', False, (), False, 0), ('poles-auto', False, (0, 2, 4), False, 2),
                                        ('mu-cross', True, (), True, 0), ('mu-poles-cross', True, (0, 1, 2), True, 2)):
-        p = _abi.Power()
-        p.nk, p.nmu, p.npoles = nk, nmu if mu else 0, len(poles)
-        for i, ell in enumerate(poles):
-            p.poles[i] = ell
-        p.hermitian, p.deconv_pow, p.volume = 1, dp, float(numpy.prod(box))
-        p.los[nd - 1] = 1.0
-        s1 = 4 + 2 * len(poles)
+        bins = _Binning(nd, 'kedges', numpy.linspace(0, 1.2 * kny, nk + 1),
+                        numpy.linspace(-1, 1, nmu + 1) if mu else None, None, poles, PowerResult, hermitian=1,
+                        deconv_pow=dp, volume=numpy.prod(box))
+        p, ke, me, s1 = bins.p, bins.et, bins.mt, bins.s1
         other = b if cross else None
 
         def project():
-            acc = torch.zeros(nk * s1 + nk * p.nmu * 5, dtype=torch.float64, device=dev)
-            be.power_project(p, a, other, start, nmesh, box, ke, me if mu else None, acc)
+            acc = bins.zeros()
+            be.power_project(p, a, other, start, nmesh, box, ke, me, acc)
             return acc
         report_sums(tag, 'power_project', form, 'acc', project)
         acc = project()
         report(tag, 'power_project', form, 'counts', torch.cat([acc[:nk * s1].view(nk, s1)[:, 0],
                                                                 acc[nk * s1:].view(-1, 5)[:, 0]]))
-        ncoef = nk * (2 + 2 * len(poles)) + nk * p.nmu * 2
+        ncoef = nk * bins.c1 + nk * p.nmu * bins.c2
         coef = torch.from_numpy(numpy.cos(numpy.arange(float(ncoef)))).to(dev)
         ga = blank(shape, oout, cdt, dev)
         gb = blank(shape, oout, cdt, dev) if cross else None
-        be.power_vjp(p, a, other, ga, gb, start, nmesh, box, ke, me if mu else None, coef)
+        be.power_vjp(p, a, other, ga, gb, start, nmesh, box, ke, me, coef)
         report(tag, 'power_vjp', form, 'grad_a', ga)
         if cross:
             report(tag, 'power_vjp', form, 'grad_b', gb)

@@ -24,8 +24,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from pmesh_amd import _abi, backend  # noqa: E402
+from pmesh_amd import backend  # noqa: E402
 from pmesh_amd.pm import ParticleMesh  # noqa: E402
+from pmesh_amd.power import PowerResult, _Binning  # noqa: E402
 from pmesh_amd.transfer import Tabulated  # noqa: E402
 
 
@@ -47,19 +48,10 @@ def power_calls(c, other, ga, gb, ke, me, poles):
     """the forward and the adjoint entries alone, on the same fields and bins"""
     be = backend.get()
     pm = c.pm
-    p = _abi.Power()
-    p.nk = len(ke) - 1
-    p.nmu = 0 if me is None else len(me) - 1
-    p.npoles = len(poles)
-    for i, ell in enumerate(poles):
-        p.poles[i] = ell
-    p.hermitian = 1
-    p.volume = float(numpy.prod(pm.BoxSize))
-    p.los[len(pm.Nmesh) - 1] = 1.0
-    acc = torch.zeros(p.nk * (4 + 2 * len(poles)) + p.nk * p.nmu * 5, dtype=torch.float64, device=be.device)
-    coef = torch.rand(p.nk * (2 + 2 * len(poles)) + p.nk * p.nmu * 2, dtype=torch.float64, device=be.device)
-    kt = torch.from_numpy(ke).to(be.device)
-    mt = torch.from_numpy(me).to(be.device) if me is not None else None
+    bins = _Binning(len(pm.Nmesh), 'kedges', ke, me, None, poles, PowerResult, hermitian=1,
+                    volume=numpy.prod(pm.BoxSize))            # the package's own struct, edges and table widths
+    p, kt, mt, acc = bins.p, bins.et, bins.mt, bins.zeros()
+    coef = torch.rand(p.nk * bins.c1 + p.nk * p.nmu * bins.c2, dtype=torch.float64, device=be.device)
     av, bv = c.value, (other.value if other is not None else None)
     gav, gbv = ga.value, (gb.value if other is not None else None)
 

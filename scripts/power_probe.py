@@ -25,9 +25,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from pmesh_amd import _abi, backend  # noqa: E402
+from pmesh_amd import backend  # noqa: E402
 from pmesh_amd.pm import ParticleMesh  # noqa: E402
-from pmesh_amd.power import power_spectrum  # noqa: E402
+from pmesh_amd.power import PowerResult, _Binning, power_spectrum  # noqa: E402
 
 COPY_RATE = 5.6e12
 
@@ -50,19 +50,9 @@ def kernel_call(c, other, ke, me, poles):
     """the entry alone (what power_spectrum launches), on a zeroed accumulator"""
     be = backend.get()
     pm = c.pm
-    p = _abi.Power()
-    p.nk = len(ke) - 1
-    p.nmu = 0 if me is None else len(me) - 1
-    p.npoles = len(poles)
-    for i, ell in enumerate(poles):
-        p.poles[i] = ell
-    p.hermitian = 1
-    p.volume = float(numpy.prod(pm.BoxSize))
-    p.los[len(pm.Nmesh) - 1] = 1.0
-    s1 = 4 + 2 * len(poles)
-    acc = torch.zeros(p.nk * s1 + p.nk * p.nmu * 5, dtype=torch.float64, device=be.device)
-    kt = torch.from_numpy(ke).to(be.device)
-    mt = torch.from_numpy(me).to(be.device) if me is not None else None
+    bins = _Binning(len(pm.Nmesh), 'kedges', ke, me, None, poles, PowerResult, hermitian=1,
+                    volume=numpy.prod(pm.BoxSize))            # the package's own struct, edges and table widths
+    p, kt, mt, acc = bins.p, bins.et, bins.mt, bins.zeros()
     av, bv = c.value, (other.value if other is not None else None)
 
     def run():

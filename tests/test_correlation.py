@@ -833,3 +833,9 @@ def test_corr_kernels_compile_without_scratch():
     for name, r in t.items():
         assert r['ScratchSize'] == 0, (name, r)
         assert r['VGPRs'] <= 168, (name, r)      # the bound of test_power.py: three or more waves per SIMD
+        # waves per SIMD of <T, MU, POLES> without options / with the (r, mu) table or the multipoles / with both
+        options = ('Lb1ELb' in name) + ('ELb1EEE' in name)
+        if 'corr_kernel' in name:
+            assert r['Occupancy'] >= (8, 5, 4)[options], (name, r)
+        elif 'corr_vjp_kernel' in name:
+            assert r['Occupancy'] >= (8, 7, 7)[options], (name, r)

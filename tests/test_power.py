@@ -409,3 +409,5 @@ def test_power_kernels_compile_without_scratch():
     for name, r in kernels.items():
         assert r['ScratchSize'] == 0, (name, r)
         assert r['VGPRs'] <= 168, (name, r)      # three or more waves per SIMD
+        # power_kernel<T, MU, POLES>: four waves per SIMD without the (k, mu) table and the multipoles, three with either
+        assert r['Occupancy'] >= (4 if 'Lb0ELb0E' in name else 3), (name, r)

@@ -692,3 +692,4 @@ def test_power_gradient_kernels_compile_without_scratch():
     for name, r in kernels.items():
         assert r['ScratchSize'] == 0, (name, r)
         assert r['VGPRs'] <= 128, (name, r)      # four waves per SIMD
+        assert r['Occupancy'] >= 4, (name, r)    # with the (k, mu) table and the multipoles as well
