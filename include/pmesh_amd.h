@@ -971,6 +971,55 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
                        const pmx_vec *vel, const double *ref, int64_t ngroups, const double *boxsize, double *out,
                        void *stream);
 
+/* ---- binned pair counts of particles (what nbodykit's SimulationBoxPairCount does on the host with Corrfunc;
+ * pmesh_amd.paircount) ------------------------------------------------------------------------------------------------
+ * The rule.
+ *   rows     pos1 and pos2 are (n, ndim) rows, ndim 1 to 3, float or double (a float is widened exactly); all arithmetic
+ *            is in double, every operation rounding once.  Rows are wrapped as above; dx_d is the minimum image of the
+ *            difference of the wrapped rows as above; r2 = sum_d dx_d^2 accumulated in the order d = 0, 1, 2.
+ *   modes    PMX_PAIRS_1D bins by r, PMX_PAIRS_2D by (r, mu), PMX_PAIRS_PROJECTED by (rp, pi); the last two need
+ *            ndim == 3 and a line-of-sight axis los in {0, 1, 2}.
+ *   edges    e2[k] = edges[k] * edges[k] is formed by the caller, edges increasing and finite, edges[0] >= 0.  A pair is
+ *            in r-bin k when e2[k] <= q < e2[k + 1]; q = r2 in the modes 1D and 2D, q = rp2 in the projected mode: the
+ *            sum of the two dx_d^2 with d != los in ascending d.  Pairs outside [e2[0], e2[nr]) are not counted.  No
+ *            square root is taken to choose a bin.
+ *   mu       (2D) sub[k] = m2[k] = muedges[k]^2, muedges increasing from 0 to 1.  With z2 = dx_los^2 the mu-bin is the
+ *            number of k in 1 .. nsub - 1 with z2 >= m2[k] * r2: no division; mu = 1 lands in the last bin.  A pair with
+ *            r2 == 0 goes to mu-bin 0.
+ *   pi       (projected) sub[k] = piedges[k], increasing from 0.  With a = |dx_los| the pi-bin is the number of k in
+ *            1 .. nsub - 1 with a >= piedges[k]; pairs with a >= piedges[nsub] are not counted.
+ *   pairs    every (slot of the primaries, slot of the secondaries), coincident rows included.  The entry knows no row
+ *            identity: a caller that passes one set as both subtracts its self pairs, which have r2 == 0 exactly and sit
+ *            in bin (0, 0) when edges[0] == 0 and nowhere otherwise.
+ *   sums     per bin: npairs (int64, exact); wnpairs = sum w1_i w2_j (double); rsum = sum w1_i w2_j sqrt(q) (double).
+ *            The order of the double sums is unspecified: their last bits may differ from run to run; npairs never does.
+ * The bin of a pair is r-bin * nsub + sub-bin (nsub = 1 in the mode 1D); nr * nsub <= PMX_PAIRS_MAX_BINS. */
+#define PMX_PAIRS_MAX_BINS 4096          /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
+#define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
+#define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
+#define PMX_PAIRS_PROJECTED 2            /* bins of (rp, pi) */
+
+/* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
+ * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
+ * The primaries: spos1 (DEVICE double (n1, ndim) contiguous), order1 and cell_of1 are what pmx_fof_cells / pmx_fof_fill
+ * left of pos1: the wrapped rows in cell order, the row of every slot, the flat cell of every ROW.  The secondaries: spos2,
+ * order2, cell_start2 (prod(ncell) + 1 entries) likewise of pos2, on the SAME grid (ncell, periodic, boxsize as passed
+ * to pmx_fof_cells for both).  The same arrays may be passed for both sets.  The cell_start of the primaries is not
+ * needed: one lane per slot of the primaries walks the 3^ndim neighbouring cells of its row in the secondaries.
+ * weight1 / weight2: one column of n1 / n2 floats or doubles in ROW order (read through order1 / order2), NULL for 1.
+ * With both NULL no weight is read and wnpairs[b] += (double)(the count).
+ * e2: DEVICE double, nr + 1 entries.  sub: DEVICE double, nsub + 1 entries, m2 (2D) or piedges (projected); NULL and
+ * nsub = 1 in the mode 1D.  los is ignored in the mode 1D.
+ * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
+ * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
+ * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)
+ * per visited pair, the latter from cache: the lanes of a wave share their neighbouring cells. */
+int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t n1, const double *spos1, const int32_t *order1,
+                    const int32_t *cell_of1, const pmx_vec *weight1, int64_t n2, const double *spos2,
+                    const int32_t *order2, const int32_t *cell_start2, const pmx_vec *weight2, const int64_t *ncell,
+                    int32_t periodic, const double *boxsize, int32_t nr, const double *e2, int32_t nsub,
+                    const double *sub, int64_t *npairs, double *wnpairs, double *rsum, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -488,6 +488,25 @@ class HipBackend(object):
                   C.byref(mv) if mass is not None else None, C.byref(vv) if vel is not None else None,
                   ref.data_ptr(), out.shape[0] - 1, _abi.f64arr(boxsize, 3), out.data_ptr(), self.stream())
 
+    # -- binned pair counts ------------------------------------------------------
+    def pair_counts(self, mode, los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2, ncell,
+                    periodic, boxsize, e2, sub, npairs, wnpairs, rsum):
+        """the binned sums over the pairs of the primaries (spos1, order1, cell_of1: what fof_cells / fof_fill left of
+        them) with the secondaries (spos2, order2, cell_start2, of the same grid) added into the zeroed tensors `npairs`
+        (int64), `wnpairs` and `rsum` (float64) of nr * nsub entries.  mode: PMX_PAIRS_*; e2: the nr + 1 squared edges
+        on the device; sub: the nsub + 1 squared mu edges or pi edges on the device, None in the mode 1D; weight1 /
+        weight2: (n,) or (n, 1) float tensors in row order, or None (pmx_pair_counts)"""
+        if spos1.shape[0] == 0 or spos2.shape[0] == 0:
+            return
+        wv1, wv2 = _arrays.vec(weight1), _arrays.vec(weight2)
+        self.call('pair_counts', spos1.shape[1], int(mode), int(los), spos1.shape[0], spos1.data_ptr(),
+                  order1.data_ptr(), cell_of1.data_ptr(), C.byref(wv1) if weight1 is not None else None,
+                  spos2.shape[0], spos2.data_ptr(), order2.data_ptr(), cell_start2.data_ptr(),
+                  C.byref(wv2) if weight2 is not None else None, _abi.i64arr(ncell, 3), int(periodic),
+                  _abi.f64arr(boxsize, 3), e2.numel() - 1, e2.data_ptr(), sub.numel() - 1 if sub is not None else 1,
+                  sub.data_ptr() if sub is not None else None, npairs.data_ptr(), wnpairs.data_ptr(), rsum.data_ptr(),
+                  self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""

@@ -1,0 +1,261 @@
+// pmx_pairs.hip — binned pair counts of particles (include/pmesh_amd.h: pmx_pair_counts; pmesh_amd/paircount.py).
+//
+// Replaces what a caller of the reference does on the host for xi(r) of a catalogue (nbodykit's SimulationBoxPairCount:
+// Corrfunc over the rows copied over PCIe).  The rule, restated from the header:
+//   rows     (n, ndim) rows wrapped into [0, L_d) by FoF's rule; dx_d the minimum image of the wrapped rows; all
+//            arithmetic in double, every operation rounded once; r2 = sum_d dx_d^2 in the order d = 0, 1, 2
+//   edges    a pair is in r-bin k when e2[k] <= q < e2[k + 1], e2 the squared edges formed on the host; q = r2 (1D, 2D)
+//            or rp2, the sum of the two dx_d^2 with d != los in ascending d (projected); no square root chooses a bin
+//   mu       the mu-bin is the number of k in 1 .. nmu - 1 with dx_los^2 >= m2[k] * r2; r2 == 0 goes to mu-bin 0
+//   pi       the pi-bin is the number of k in 1 .. npi - 1 with |dx_los| >= piedges[k]; |dx_los| >= piedges[npi] is
+//            not counted
+//   sums     npairs exact; wnpairs = sum w1 w2 and rsum = sum w1 w2 sqrt(q) in double, in no particular order
+// The pass: pairs_kernel, one lane per slot of the primaries in cell order.  The lane walks the 3^ndim neighbouring
+// cells of its row in the secondaries (the walk of link_kernel, pmx_cells_dev.h); the lanes of a wave sit in one cell
+// or in adjacent ones, so they read the same secondaries at the same time: broadcast loads from cache.  Every pair
+// inside the edges makes one 32-bit integer and one (weighted: two) double LDS atomic on the workgroup's histogram;
+// at its end the workgroup makes one global atomic per array and non-zero bin.  (Replicating the histogram over the
+// lanes, slot = bin * R + lane % R, so that the lanes of a wave that meet in one outer bin do not meet on one address,
+// measured nothing at 20 bins, and neither did removing the LDS atomics altogether: DESIGN.md 5.7.)  No lane waits for
+// another: the only barriers are the two around the walk.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "pmx_cells_dev.h"
+#include "pmx_common.h"
+
+namespace pmx {
+
+constexpr int PBLOCK = 256;
+constexpr int PAIRS_SLOTS_SMALL = 1024;          // the bins of the histogram of the small form: 12 / 20 KB
+constexpr int PAIRS_SLOTS_BIG = PMX_PAIRS_MAX_BINS;   // of the form for many bins: 48 / 80 KB, two workgroups per CU
+constexpr int PAIRS_EDGES_LDS = 128;             // up to this many bins along an axis, its edges are searched in LDS
+constexpr int PAIRS_LINEAR = 8;                  // up to this many, by a linear walk from the outermost
+// the secondaries of one launch: 256 lanes x 2^23 slots = 2^31 pairs at most per workgroup and 32-bit count
+constexpr int64_t PAIRS_WINDOW = (int64_t)1 << 23;
+
+struct PArgs {
+    FGeom g;
+    int64_t n1, n2;
+    int32_t slo, shi;                            // the slots of the secondaries of this launch
+    const double *spos1, *spos2;
+    const int32_t *order1, *cell_of1, *order2, *cell_start2;
+    DVec w1, w2;
+    int64_t ncells;
+    int32_t nr, nsub, nbins, los;
+    const double *e2, *sub;
+    unsigned long long *npairs;
+    double *wnpairs, *rsum;
+};
+
+// the minimum image of dx = w - w', both in [0, L): fof_image without its division where the quotient is known.
+// |dx| <= L / 4 (exact: a power of two times L) gives |dx / L| <= 1/4 after rounding, rint of it 0, and dx - L * 0 = dx.
+__device__ __forceinline__ double pair_image(double dx, double L, double quarter)
+{
+    return fabs(dx) <= quarter ? dx : fof_image(dx, L);
+}
+
+// the largest k in 0 .. n - 1 with q >= tab[k], given q >= tab[0]; tab increasing
+template <typename P> __device__ __forceinline__ int pair_bin(P tab, int n, double q)
+{
+    if (n <= PAIRS_LINEAR) {
+        int k = n - 1;
+        while (k > 0 && q < tab[k]) k--;
+        return k;
+    }
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (q >= tab[mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the number of k in 1 .. n - 1 with z2 >= tab[k] * r2 (the products do not decrease with k: the test holds for a
+// prefix of them)
+template <typename P> __device__ __forceinline__ int pair_mu_bin(P tab, int n, double z2, double r2)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (z2 >= tab[mid] * r2) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int NDIM, int MODE, bool WEIGHTED, int SLOTS>
+__global__ void __launch_bounds__(PBLOCK) pairs_kernel(PArgs a)
+{
+    __shared__ uint32_t hcount[SLOTS];
+    __shared__ double hrsum[SLOTS];
+    __shared__ double hwsum[WEIGHTED ? SLOTS : 1];
+    // (the weighted form for many bins fills its 80 KB with the histogram: it searches the edges in global memory)
+    constexpr int EL = WEIGHTED && SLOTS > PAIRS_SLOTS_SMALL ? 0 : PAIRS_EDGES_LDS;
+    __shared__ double se2[EL + 1];
+    __shared__ double ssub[MODE == PMX_PAIRS_1D ? 1 : EL + 1];
+    const int tid = threadIdx.x;
+    const int used = min(a.nbins, SLOTS);
+    for (int s = tid; s < used; s += PBLOCK) {
+        hcount[s] = 0;
+        hrsum[s] = 0;
+        if (WEIGHTED) hwsum[s] = 0;
+    }
+    const bool e_lds = EL > 0 && a.nr <= EL, s_lds = EL > 0 && a.nsub <= EL;
+    if (e_lds)
+        for (int s = tid; s <= a.nr; s += PBLOCK) se2[s] = a.e2[s];
+    if (MODE != PMX_PAIRS_1D && s_lds)
+        for (int s = tid; s <= a.nsub; s += PBLOCK) ssub[s] = a.sub[s];
+    __syncthreads();
+
+    const int64_t k = (int64_t)blockIdx.x * PBLOCK + tid;
+    int32_t i = -1, flat = -1;
+    if (k < a.n1) i = a.order1[k];
+    if (i >= 0 && i < a.n1) flat = a.cell_of1[i];               // (always, with the order fill_kernel left)
+    if (flat >= 0 && flat < a.ncells) {
+        const FGeom &g = a.g;
+        double x[NDIM], quarter[NDIM];
+#pragma unroll
+        for (int d = 0; d < NDIM; d++) {
+            x[d] = a.spos1[k * NDIM + d];
+            quarter[d] = 0.25 * g.L[d];
+        }
+        double w1 = 1.0;
+        if (WEIGHTED && a.w1.data) w1 = a.w1.get(i, 0);
+        const double qlo = a.e2[0], qhi = a.e2[a.nr];
+        const double pimax = MODE == PMX_PAIRS_PROJECTED ? a.sub[a.nsub] : 0.0;
+        int32_t c[3];
+        fof_cell_axes<NDIM>(g, flat, c);
+        for (int nb = 0; nb < fof_neighbours<NDIM>(); nb++) {
+            int32_t cell;
+            if (!fof_neighbour<NDIM>(g, c, nb, cell)) continue;
+            const int32_t s0 = max(a.cell_start2[cell], a.slo), s1 = min(a.cell_start2[cell + 1], a.shi);
+            for (int32_t s = s0; s < s1; s++) {
+                double dx[3] = {0, 0, 0};
+#pragma unroll
+                for (int d = 0; d < NDIM; d++)
+                    dx[d] = pair_image(x[d] - a.spos2[(int64_t)s * NDIM + d], g.L[d], quarter[d]);
+                double q = 0, z = 0;
+                if (MODE == PMX_PAIRS_PROJECTED) {
+#pragma unroll
+                    for (int d = 0; d < NDIM; d++)
+                        if (d != a.los) q += dx[d] * dx[d];
+                } else {
+#pragma unroll
+                    for (int d = 0; d < NDIM; d++) q += dx[d] * dx[d];
+                }
+                if (!(q >= qlo && q < qhi)) continue;
+                if (MODE != PMX_PAIRS_1D) z = a.los == 0 ? dx[0] : (a.los == 1 ? dx[1] : dx[2]);
+                int bin = e_lds ? pair_bin(se2, a.nr, q) : pair_bin(a.e2, a.nr, q);
+                if (MODE == PMX_PAIRS_2D) {
+                    const double z2 = z * z;
+                    int m = 0;
+                    if (q > 0) m = s_lds ? pair_mu_bin(ssub, a.nsub, z2, q) : pair_mu_bin(a.sub, a.nsub, z2, q);
+                    bin = bin * a.nsub + m;
+                }
+                if (MODE == PMX_PAIRS_PROJECTED) {
+                    const double az = fabs(z);
+                    if (!(az < pimax)) continue;
+                    // (az >= 0 = piedges[0] where the edges are the rule's; anything below the first edge goes to bin 0)
+                    bin = bin * a.nsub + (s_lds ? pair_bin(ssub, a.nsub, az) : pair_bin(a.sub, a.nsub, az));
+                }
+                const int slot = bin;
+                if (slot < 0 || slot >= used) continue;            // (never: 0 <= bin < nbins)
+                const double r = sqrt(q);
+                if (WEIGHTED) {
+                    double w = w1;
+                    if (a.w2.data) {
+                        const int32_t j = a.order2[s];
+                        if (j < 0 || j >= a.n2) continue;          // (never, with the order fill_kernel left)
+                        w = w1 * a.w2.get(j, 0);
+                    }
+                    atomicAdd(&hcount[slot], 1u);
+                    atomicAdd(&hwsum[slot], w);
+                    atomicAdd(&hrsum[slot], w * r);
+                } else {
+                    atomicAdd(&hcount[slot], 1u);
+                    atomicAdd(&hrsum[slot], r);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    for (int b = tid; b < used; b += PBLOCK) {
+        const unsigned long long n = hcount[b];
+        if (n == 0) continue;
+        atomicAdd(&a.npairs[b], n);
+        atomicAdd(&a.wnpairs[b], WEIGHTED ? hwsum[b] : (double)n);
+        atomicAdd(&a.rsum[b], hrsum[b]);
+    }
+}
+
+}  // namespace pmx
+
+using namespace pmx;
+
+template <int NDIM, int MODE> static void pairs_launch(const PArgs &a, bool weighted, unsigned grid, hipStream_t st)
+{
+    const bool big = a.nbins > PAIRS_SLOTS_SMALL;
+    with_bool(weighted, [&](auto w) {
+        if (big) pairs_kernel<NDIM, MODE, decltype(w)::value, PAIRS_SLOTS_BIG><<<grid, PBLOCK, 0, st>>>(a);
+        else pairs_kernel<NDIM, MODE, decltype(w)::value, PAIRS_SLOTS_SMALL><<<grid, PBLOCK, 0, st>>>(a);
+    });
+}
+
+extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t n1, const double *spos1,
+                               const int32_t *order1, const int32_t *cell_of1, const pmx_vec *weight1, int64_t n2,
+                               const double *spos2, const int32_t *order2, const int32_t *cell_start2,
+                               const pmx_vec *weight2, const int64_t *ncell, int32_t periodic, const double *boxsize,
+                               int32_t nr, const double *e2, int32_t nsub, const double *sub, int64_t *npairs,
+                               double *wnpairs, double *rsum, void *stream)
+{
+    PArgs a;
+    const int rc = fof_geom(ndim, boxsize, nullptr, nullptr, ncell, periodic, a.g, &a.ncells);
+    if (rc != PMX_OK) return rc;
+    PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED, PMX_EINVAL, "bad mode");
+    PMX_REQUIRE(mode == PMX_PAIRS_1D || (ndim == 3 && los >= 0 && los <= 2), PMX_EINVAL,
+                "the modes 2D and projected need three dimensions and a line of sight along one of them");
+    PMX_REQUIRE(nr >= 1 && nsub >= 1 && (mode != PMX_PAIRS_1D || nsub == 1), PMX_EINVAL, "bad bin counts");
+    PMX_REQUIRE((int64_t)nr * nsub <= PMX_PAIRS_MAX_BINS, PMX_EINVAL, "more than PMX_PAIRS_MAX_BINS bins");
+    PMX_REQUIRE(n1 >= 0 && n2 >= 0, PMX_EINVAL, "bad arguments");
+    PMX_REQUIRE(n1 <= PMX_FOF_MAX_ROWS && n2 <= PMX_FOF_MAX_ROWS, PMX_EUNSUPPORTED,
+                "more than 2^31 - 1 rows: slots are 32-bit");
+    if (n1 == 0 || n2 == 0) return PMX_OK;
+    PMX_REQUIRE(spos1 && order1 && cell_of1 && spos2 && order2 && cell_start2, PMX_EINVAL, "bad arguments");
+    PMX_REQUIRE(e2 && (mode == PMX_PAIRS_1D || sub) && npairs && wnpairs && rsum, PMX_EINVAL, "bad arguments");
+    const bool has1 = weight1 && weight1->data, has2 = weight2 && weight2->data;
+    PMX_REQUIRE(!has1 || vec_ok(weight1), PMX_EINVAL, "weight1 must be float or double");
+    PMX_REQUIRE(!has2 || vec_ok(weight2), PMX_EINVAL, "weight2 must be float or double");
+    a.n1 = n1;
+    a.n2 = n2;
+    a.spos1 = spos1;
+    a.spos2 = spos2;
+    a.order1 = order1;
+    a.cell_of1 = cell_of1;
+    a.order2 = order2;
+    a.cell_start2 = cell_start2;
+    a.w1 = dvec(has1 ? weight1 : nullptr);
+    a.w2 = dvec(has2 ? weight2 : nullptr);
+    a.nr = nr;
+    a.nsub = nsub;
+    a.nbins = nr * nsub;
+    a.los = mode == PMX_PAIRS_1D ? 0 : los;
+    a.e2 = e2;
+    a.sub = sub;
+    a.npairs = (unsigned long long *)npairs;
+    a.wnpairs = wnpairs;
+    a.rsum = rsum;
+    const unsigned grid = (unsigned)((n1 + PBLOCK - 1) / PBLOCK);
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t lo = 0; lo < n2; lo += PAIRS_WINDOW) {
+        a.slo = (int32_t)lo;
+        a.shi = (int32_t)(lo + PAIRS_WINDOW < n2 ? lo + PAIRS_WINDOW : n2);
+        if (mode == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, has1 || has2, grid, st);
+        else if (mode == PMX_PAIRS_PROJECTED) pairs_launch<3, PMX_PAIRS_PROJECTED>(a, has1 || has2, grid, st);
+        else with_count<3>(ndim, [&](auto nd) { pairs_launch<decltype(nd)::value, PMX_PAIRS_1D>(a, has1 || has2, grid, st); });
+    }
+    PMX_HIP_CHECK(hipGetLastError());
+    return PMX_OK;
+}

@@ -1,0 +1,272 @@
+"""Binned pair counts of particles and the two-point function from them, made on the device.
+
+What nbodykit's ``SimulationBoxPairCount`` and ``SimulationBox2PCF`` do on the host (Corrfunc over the rows copied over
+PCIe) as one entry of the C ABI (csrc/pmx_pairs.hip, include/pmesh_amd.h: pmx_pair_counts) behind the cell grid of
+pmesh_amd.fof: the rows of ``lognormal_catalog``, of an N-body run or of ``fof_catalog`` are counted without leaving
+HBM, down to separations far below the cell size of any mesh.
+
+The rule (normative; include/pmesh_amd.h restates it next to the entry point).
+
+1. Rows.  ``pos1`` and ``pos2`` are ``(n, ndim)`` rows, ``ndim = len(pm.Nmesh)`` in 1 .. 3, float64 or float32 (widened
+   exactly).  All arithmetic is in double, every operation rounded once.  Rows are wrapped by rule 2 of pmesh_amd.fof;
+   ``dx_d`` is its minimum image of the wrapped rows; ``r2 = sum_d dx_d^2`` is accumulated in the order d = 0, 1, 2.
+2. Modes.  ``'1d'`` bins by r, ``'2d'`` by (r, mu), ``'projected'`` by (rp, pi).  The last two need ndim == 3 and a
+   line-of-sight axis ``los`` in {0, 1, 2}, default 2.
+3. Edges.  ``edges`` (for r or rp) is increasing and finite with ``edges[0] >= 0``.  The host forms ``e2[k] = edges[k] *
+   edges[k]`` once, in double; no square root chooses a bin.  A pair is in r-bin k when ``e2[k] <= q < e2[k + 1]``,
+   ``q = r2`` in the modes 1d and 2d; in the projected mode ``q = rp2``, the sum of the two ``dx_d^2`` with d != los in
+   ascending d.  Pairs outside ``[e2[0], e2[-1])`` are not counted.
+4. mu bins (2d).  ``muedges`` is increasing from 0 to 1; ``m2[k] = muedges[k]^2`` is formed on the host.  With ``z2 =
+   dx_los^2`` the mu-bin is the number of k in 1 .. nmu - 1 with ``z2 >= m2[k] * r2``: no division, no square root;
+   mu = 1 lands in the last bin.  A pair with ``r2 == 0`` goes to mu-bin 0.
+5. pi bins (projected).  ``piedges`` is increasing from 0.  With ``a = |dx_los|`` the pi-bin is the number of k in
+   1 .. npi - 1 with ``a >= piedges[k]``; pairs with ``a >= piedges[-1]`` are not counted.
+6. Pairs.  Cross (``pos2`` given): every (i in pos1, j in pos2), coincident rows included.  Auto (``pos2 is None``):
+   every ordered pair i != j of pos1, so each unordered pair counts twice, as Corrfunc and nbodykit report it; self
+   pairs are excluded.  The identity of a row is its global index, not its position: two different rows at one
+   position are a pair at r2 = 0.
+7. Sums, per bin.  ``npairs`` is int64 and exact; ``wnpairs = sum w1_i w2_j`` and ``rsum = sum w1_i w2_j r`` are double
+   sums, ``r = sqrt(q)``.  Weights are ``(n,)`` float rows, or None for 1.  The order of the double sums is unspecified:
+   their last bits may vary from run to run.  npairs never varies.
+8. Search radius.  ``b = edges[-1]``, in the projected mode ``max(edges[-1], piedges[-1])``; b is finite, positive and
+   ``2 b <= min_d L_d``, otherwise ValueError on every rank.  Rows with a coordinate that is not finite raise
+   ValueError with their number, on every rank.
+9. Bin limit.  ``nr``, ``nr * nmu`` or ``nrp * npi`` is at most PMX_PAIRS_MAX_BINS (4096); more raise ValueError.
+
+    from pmesh_amd.paircount import pair_counts, pair_correlation
+    pc = pair_counts(pm, pos, edges)                               # auto, bins of r
+    pc.npairs, pc.wnpairs, pc.rsum, pc.rmean
+    xi, pc = pair_correlation(pm, pos, edges, mode='2d', Nmu=100)  # xi(r, mu), natural estimator, analytic randoms
+
+On one rank both sets are sorted into one periodic cell grid of side >= b (``fof.cell_grid`` / ``fof.cell_sort``) and
+one kernel counts.  On several ranks the primaries go to their owners (``pm.decompose`` without ghosts), the
+secondaries to every rank whose block they lie within b of; each rank counts its primaries against its secondaries,
+and one allreduce sums the three arrays: every ordered pair is counted on exactly one rank.  In the auto form the self
+pairs are subtracted on the host: they have r2 == 0 exactly, so they sit in bin (0, 0) when edges[0] == 0 and nowhere
+otherwise.
+"""
+import numpy
+import torch
+
+from . import _abi, backend
+from .fof import MAX_ROWS, _allsum, _block, _rows, _together, cell_grid, cell_sort
+
+MAX_BINS = _abi.PMX_PAIRS_MAX_BINS
+MODES = {'1d': _abi.PMX_PAIRS_1D, '2d': _abi.PMX_PAIRS_2D, 'projected': _abi.PMX_PAIRS_PROJECTED}
+
+
+class PairCounts(object):
+    """The binned sums over the pairs, identical on every rank: ``npairs`` (int64), ``wnpairs``, ``rsum`` and ``rmean =
+    rsum / wnpairs`` (float64; nan where the bin holds no pair), device tensors of the shape (nr,), (nr, nmu) or (nrp,
+    npi); ``edges`` and ``muedges`` / ``piedges`` (numpy arrays, None where the mode has none), ``mode``, ``los``,
+    ``auto``; ``W1`` and ``W2`` (the sums of the weights of the two sets over all ranks; the row counts without
+    weights), ``W2sum`` (auto: the sum of w^2; cross: 0), ``BoxSize``."""
+
+    def __init__(self, npairs, wnpairs, rsum, edges, muedges, piedges, mode, los, auto, W1, W2, W2sum, BoxSize):
+        self.npairs, self.wnpairs, self.rsum = npairs, wnpairs, rsum
+        nan = torch.full_like(rsum, float('nan'))
+        self.rmean = torch.where(npairs > 0, rsum / torch.where(npairs > 0, wnpairs, torch.ones_like(wnpairs)), nan)
+        self.edges, self.muedges, self.piedges = edges, muedges, piedges
+        self.mode, self.los, self.auto = mode, los, auto
+        self.W1, self.W2, self.W2sum, self.BoxSize = W1, W2, W2sum, BoxSize
+
+
+def bin_volumes(edges, ndim, mode='1d', sub=None):
+    """V_bin of every bin: the volume in which the second row of a pair of that bin lies around the first.
+
+    1d: 4 pi / 3 (e_hi^3 - e_lo^3) for ndim 3, pi (e_hi^2 - e_lo^2) for ndim 2, 2 (e_hi - e_lo) for ndim 1.  2d: the 3-d
+    value times (mu_hi - mu_lo).  projected: pi (rp_hi^2 - rp_lo^2) * 2 (pi_hi - pi_lo)."""
+    e = numpy.asarray(edges, dtype='f8')
+    if mode == 'projected':
+        s = numpy.asarray(sub, dtype='f8')
+        return (numpy.pi * (e[1:] ** 2 - e[:-1] ** 2))[:, None] * (2 * (s[1:] - s[:-1]))[None, :]
+    if ndim == 3:
+        v = 4 * numpy.pi / 3 * (e[1:] ** 3 - e[:-1] ** 3)
+    elif ndim == 2:
+        v = numpy.pi * (e[1:] ** 2 - e[:-1] ** 2)
+    else:
+        v = 2 * (e[1:] - e[:-1])
+    if mode == '2d':
+        s = numpy.asarray(sub, dtype='f8')
+        return v[:, None] * (s[1:] - s[:-1])[None, :]
+    return v
+
+
+def _edges(x, what, first=None, last=None):
+    """(the edges as a float64 numpy array, error)"""
+    try:
+        e = numpy.array(x, dtype='f8')
+    except (TypeError, ValueError):
+        return None, ValueError('%s must be a sequence of numbers' % what)
+    if e.ndim != 1 or len(e) < 2 or not numpy.isfinite(e).all() or not (numpy.diff(e) > 0).all() or e[0] < 0:
+        return None, ValueError('%s must be increasing and finite, at least two of them, the first >= 0' % what)
+    if first is not None and e[0] != first:
+        return None, ValueError('%s must start at %g' % (what, first))
+    if last is not None and e[-1] != last:
+        return None, ValueError('%s must end at %g' % (what, last))
+    return e, None
+
+
+def _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los):
+    """(edges, sub edges or None, error) of the arguments that say how to bin"""
+    if mode not in MODES:
+        return None, None, ValueError("mode must be '1d', '2d' or 'projected', not %r" % (mode,))
+    e, error = _edges(edges, 'edges')
+    if error is not None:
+        return None, None, error
+    sub = None
+    if mode != '1d':
+        if nd != 3:
+            return None, None, ValueError("mode=%r needs a mesh of three dimensions, not %d" % (mode, nd))
+        if los not in (0, 1, 2):
+            return None, None, ValueError('los must be 0, 1 or 2, not %r' % (los,))
+        if mode == '2d':
+            if muedges is None and Nmu is not None and int(Nmu) == Nmu and Nmu >= 1:
+                muedges = numpy.linspace(0.0, 1.0, int(Nmu) + 1)
+            if muedges is None:
+                return None, None, ValueError("mode='2d' needs muedges, or Nmu: a positive integer")
+            sub, error = _edges(muedges, 'muedges', first=0.0, last=1.0)
+        else:
+            if piedges is None and pimax is not None and int(pimax) == pimax and pimax >= 1:
+                piedges = numpy.arange(0.0, int(pimax) + 1)
+            if piedges is None:
+                return None, None, ValueError("mode='projected' needs piedges, or pimax: a positive integer")
+            sub, error = _edges(piedges, 'piedges', first=0.0)
+        if error is not None:
+            return None, None, error
+    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
+    if nbins > MAX_BINS:
+        return None, None, ValueError('%d bins: at most %d (PMX_PAIRS_MAX_BINS)' % (nbins, MAX_BINS))
+    return e, sub, None
+
+
+def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub):
+    """The three arrays of the rows of one rank on the cell grid `grid` (of fof.cell_grid): every row of `pos1` with
+    every row of `pos2` (None: with every row of pos1, itself included: the caller subtracts the self pairs).  e2 and
+    sub: device tensors.  Returns (npairs, wnpairs, rsum), flat."""
+    dev = pos1.device
+    nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
+    npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
+    wnpairs = torch.zeros(nbins, dtype=torch.float64, device=dev)
+    rsum = torch.zeros(nbins, dtype=torch.float64, device=dev)
+    _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
+    if pos2 is None:
+        order2, cell_start2, spos2, weight2 = order1, cell_start1, spos1, weight1
+    else:
+        _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
+    be.pair_counts(MODES[mode], los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2, grid[0],
+                   grid[3], box, e2, sub, npairs, wnpairs, rsum)
+    return npairs, wnpairs, rsum
+
+
+def _weight_sums(comm, w, n):
+    """(sum of w, sum of w^2) over all ranks, as floats; the row count twice without weights"""
+    if w is None:
+        total = float(comm.allreduce(n)) if comm.size > 1 else float(n)
+        return total, total
+    w = w.to(torch.float64)
+    s = torch.stack([w.sum(), (w * w).sum()])
+    s = _allsum(comm, s).cpu()
+    return float(s[0]), float(s[1])
+
+
+def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None, Nmu=None,
+                piedges=None, pimax=None, los=2):
+    """The binned pair counts of the rows by the rule of the module docstring: a PairCounts.
+
+    pm : ParticleMesh of 1, 2 or 3 dimensions; its BoxSize is the periodic box, its communicator the ranks.
+    pos1 : (n, ndim) float64 or float32, device tensor or numpy array, this rank's rows (any number, none included).
+    edges : the nr + 1 edges of the bins of r (of rp in the projected mode), in box units.
+    pos2 : the rows of a second set for the cross counts, or None: the ordered pairs i != j of pos1.
+    weight1, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
+    mode : '1d', '2d' or 'projected'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or pimax for bins
+        of unit width in [0, pimax]: nbodykit's conventions.  los : the axis of the line of sight.
+
+    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
+    ValueError: slots are 32-bit.
+    """
+    be = backend.get()
+    comm = pm.comm
+    nd = len(pm.Nmesh)
+    if nd > _abi.PMX_MAXDIM:
+        raise NotImplementedError('pair counts on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
+    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    auto = pos2 is None
+    e, sub, error = _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los)
+    b = None
+    if error is None:
+        b = float(max(e[-1], sub[-1])) if mode == 'projected' else float(e[-1])
+        if not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+            error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
+                               'side: %r' % b)
+    if error is None and auto and weight2 is not None:
+        error = ValueError('weight2 needs pos2')
+    rows = []
+    for what, x, ncol, of in (('pos1', pos1, nd, None), ('pos2', pos2, nd, None), ('weight1', weight1, 1, 0),
+                              ('weight2', weight2, 1, 1)):
+        t = None
+        if x is not None and error is None:
+            t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
+        rows.append(t)
+    _together(comm, error)
+    pos1, pos2, weight1, weight2 = rows
+    if weight1 is not None:
+        weight1 = weight1.reshape(-1)
+    if weight2 is not None:
+        weight2 = weight2.reshape(-1)
+    nbad = int((~torch.isfinite(pos1)).any(dim=1).sum()) + (0 if auto else int((~torch.isfinite(pos2)).any(dim=1).sum()))
+    if comm.size > 1:
+        nbad = int(comm.allreduce(nbad))
+    if nbad:
+        raise ValueError('%d rows of pos1 and pos2 have a coordinate that is not finite' % nbad)
+    n1 = pos1.shape[0]
+    W1, W1sq = _weight_sums(comm, weight1, n1)
+    W2, W2sum = (W1, W1sq) if auto else (_weight_sums(comm, weight2, pos2.shape[0])[0], 0.0)
+    csize1 = int(comm.allreduce(n1)) if comm.size > 1 else n1
+    dev = be.device
+    e2 = torch.from_numpy(e * e).to(dev)
+    if sub is None:
+        subt = None
+    else:
+        subt = torch.from_numpy(sub * sub if mode == '2d' else sub).to(dev)
+    if comm.size == 1:
+        most = max(n1, 0 if auto else pos2.shape[0])
+        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
+        sums = local_counts(be, mode, los, pos1, weight1, pos2, weight2, cell_grid(most, b, box), box, e2, subt)
+    else:
+        # the primaries to their owners; the secondaries to every rank whose block they lie within b of (a hair more
+        # than b: a pair at exactly b across a block face must not depend on the rounding of the routing)
+        own = pm.decompose(pos1, smoothing=0)
+        smoothing = b * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
+        ghosts = pm.decompose(pos1 if auto else pos2, smoothing=smoothing)
+        most = max(own.recvlength, ghosts.recvlength)
+        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
+        p1 = own.exchange(pos1)
+        q1 = own.exchange(weight1) if weight1 is not None else None
+        p2 = ghosts.exchange(pos1 if auto else pos2)
+        w2 = weight1 if auto else weight2
+        q2 = ghosts.exchange(w2) if w2 is not None else None
+        lo, hi = _block(pm)
+        sums = local_counts(be, mode, los, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
+        sums = [_allsum(comm, s) for s in sums]
+    npairs, wnpairs, rsum = sums
+    if auto and e[0] == 0:
+        # the self pairs: r2 == 0 exactly, bin (0, 0)
+        npairs[0] -= csize1
+        wnpairs[0] -= W2sum
+    shape = (len(e) - 1,) if sub is None else (len(e) - 1, len(sub) - 1)
+    return PairCounts(npairs.reshape(shape), wnpairs.reshape(shape), rsum.reshape(shape), e,
+                      sub if mode == '2d' else None, sub if mode == 'projected' else None, mode, los, auto, W1, W2,
+                      W2sum, box)
+
+
+def pair_correlation(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None, Nmu=None,
+                     piedges=None, pimax=None, los=2):
+    """(xi, PairCounts): the natural estimator with analytic randoms, ``xi = wnpairs / RR - 1`` with ``RR = (W1 W2 -
+    [auto] sum w^2) V_bin / V_box`` (bin_volumes), a float64 device tensor of the shape of the counts.  The arguments
+    are those of pair_counts.  RR is host arithmetic on nbins numbers."""
+    pc = pair_counts(pm, pos1, edges, pos2, weight1, weight2, mode, muedges, Nmu, piedges, pimax, los)
+    sub = pc.muedges if mode == '2d' else pc.piedges
+    rr = (pc.W1 * pc.W2 - pc.W2sum) * bin_volumes(pc.edges, len(pc.BoxSize), mode, sub) / float(numpy.prod(pc.BoxSize))
+    xi = pc.wnpairs / torch.from_numpy(numpy.ascontiguousarray(rr)).to(pc.wnpairs.device) - 1
+    return xi, pc

@@ -1,0 +1,177 @@
+"""Times the pair-count kernel (csrc/pmx_pairs.hip) and the whole pair_counts() call on one GPU, and the host route it
+replaces on the same kind of rows.
+
+Two inputs per --rows value:
+  uniform    uniform rows in the unit box
+  lognormal  the rows of lognormal_catalog on a --mesh^3 mesh with about that many rows (bias 2)
+Per input, for b = --seps mean separations (default 0.5, 2 and 8), the auto counts in 1d with 20 linear bins of [0, b]
+and in 2d with 40 x 100 bins: pmx_pair_counts alone on the sorted rows (HIP events around the entry, one warm-up call,
+the median of --reps launches, clocks as found), the pairs it visits and counts, pairs per second by both, the cells of
+the grid and the most rows in one; the whole pair_counts() call (host clock, synchronised: the cell sort, the kernel,
+the host arithmetic).  The host route — a copy of the rows to the host, a periodic scipy.spatial.cKDTree and its
+count_neighbors at the 21 cumulative radii (1d only; it has no (r, mu) bins) — is timed on --host-rows rows drawn
+evenly from the input, at the same multiples of ITS mean separation; without scipy the copy over PCIe alone is given
+and the line says so.  One JSON line per input, b and mode.
+
+    python scripts/pairs_probe.py [--rows 1000000 10000000] [--mesh 256] [--seps 0.5 2 8] [--reps 3]
+                                  [--host-rows 1000000] [--no-host] [--no-lognormal]
+Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/pairs_probe.py ...` (a run of its
+own).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from pmesh_amd import _abi, backend  # noqa: E402
+from pmesh_amd.fof import cell_grid, cell_sort  # noqa: E402
+from pmesh_amd.mock import lognormal_catalog  # noqa: E402
+from pmesh_amd.paircount import pair_counts  # noqa: E402
+from pmesh_amd.pm import ParticleMesh  # noqa: E402
+from pmesh_amd.transfer import Tabulated  # noqa: E402
+
+
+def timed(fn, reps, prep=None):
+    """median ms of `reps` launches of fn after one warm-up; prep runs before each, outside the events"""
+    ts = []
+    for i in range(reps + 1):
+        if prep is not None:
+            prep()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        if i:
+            ts.append(a.elapsed_time(b))
+    return float(numpy.median(ts))
+
+
+def host_clock(fn, reps):
+    ts = []
+    for i in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        if i:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return float(numpy.median(ts)), r
+
+
+def host_route(pos, edges, box):
+    """the rows over PCIe, a periodic kd-tree, its cumulative counts at the edges: ms of each"""
+    t0 = time.perf_counter()
+    rows = pos.cpu().numpy()
+    t_copy = (time.perf_counter() - t0) * 1e3
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        return {'host_copy_ms': round(t_copy, 2), 'host': 'scipy is not installed: the copy alone'}
+    t0 = time.perf_counter()
+    tree = cKDTree(numpy.mod(rows, box), boxsize=box)
+    t_tree = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    cumulative = tree.count_neighbors(tree, edges)
+    t_count = (time.perf_counter() - t0) * 1e3
+    return {'host_rows': len(rows), 'host_copy_ms': round(t_copy, 2), 'host_tree_ms': round(t_tree, 1),
+            'host_count_ms': round(t_count, 1), 'host_pairs': int(cumulative[-1]) - len(rows),
+            'host_pairs_per_s': round((int(cumulative[-1]) - len(rows)) / (t_count * 1e-3), 1)}
+
+
+def probe(name, pm, pos, args):
+    be = backend.get()
+    dev = be.device
+    n, nd = pos.shape
+    box = [float(x) for x in pm.BoxSize]
+    sep = (float(numpy.prod(box)) / n) ** (1.0 / nd)
+    for mult in args.seps:
+        b = mult * sep
+        if 2 * b > min(box):
+            continue
+        grid = cell_grid(n, b, box)
+        _, cell_of, cell_start, order, spos, _ = cell_sort(be, pos, grid, box)
+        per_cell = (cell_start[1:] - cell_start[:-1]).to(torch.int64)
+        # the pairs the kernel visits: every row with every row of its 3^ndim cells (grids of fewer than three cells along
+        # an axis visit fewer; not at these sizes)
+        dense = per_cell.reshape(grid[0]).to(torch.float64)
+        near = torch.zeros_like(dense)
+        for o in numpy.ndindex(*([3] * nd)):
+            near += torch.roll(dense, [int(x) - 1 for x in o], list(range(nd)))
+        visited = float((dense * near).sum())
+        edges = numpy.linspace(0.0, b, 21)
+        for mode, e, sub in (('1d', edges, None), ('2d', numpy.linspace(0.0, b, 41), numpy.linspace(0.0, 1.0, 101))):
+            e2 = torch.from_numpy(e * e).to(dev)
+            subt = None if sub is None else torch.from_numpy(sub * sub).to(dev)
+            nbins = (len(e) - 1) * (1 if sub is None else len(sub) - 1)
+            npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
+            wn = torch.zeros(nbins, dtype=torch.float64, device=dev)
+            rs = torch.zeros(nbins, dtype=torch.float64, device=dev)
+
+            def zero():
+                npairs.zero_(), wn.zero_(), rs.zero_()
+            code = _abi.PMX_PAIRS_1D if sub is None else _abi.PMX_PAIRS_2D
+            t_kernel = timed(lambda: be.pair_counts(code, 2, spos, order, cell_of, None, spos, order, cell_start, None,
+                                                    grid[0], grid[3], box, e2, subt, npairs, wn, rs), args.reps,
+                             prep=zero)
+            counted = int(npairs.sum()) - n
+            t_call, _ = host_clock(lambda: pair_counts(pm, pos, e, mode=mode, muedges=sub), min(args.reps, 2))
+            line = {'input': name, 'rows': n, 'b_in_mean_separations': mult, 'b': b, 'mode': mode, 'bins': nbins,
+                    'cells': int(numpy.prod(grid[0])), 'max_rows_per_cell': int(per_cell.max()),
+                    'kernel_ms': round(t_kernel, 3), 'call_ms': round(t_call, 3), 'pairs_counted': counted,
+                    'pairs_visited': visited, 'counted_per_s': round(counted / (t_kernel * 1e-3), 1),
+                    'visited_per_s': round(visited / (t_kernel * 1e-3), 1)}
+            if mode == '1d' and not args.no_host:
+                m = min(n, args.host_rows)
+                pick = pos[:: max(n // m, 1)][:m].contiguous()
+                hsep = (float(numpy.prod(box)) / len(pick)) ** (1.0 / nd)
+                if 2 * mult * hsep <= min(box):
+                    line.update(host_route(pick, numpy.linspace(0.0, mult * hsep, 21), box))
+            print(json.dumps(line), flush=True)
+        del cell_of, cell_start, order, spos
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rows', type=int, nargs='+', default=[10 ** 6, 10 ** 7])
+    ap.add_argument('--mesh', type=int, default=256)
+    ap.add_argument('--seps', type=float, nargs='+', default=[0.5, 2.0, 8.0])
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--host-rows', type=int, default=10 ** 6)
+    ap.add_argument('--no-host', action='store_true')
+    ap.add_argument('--no-lognormal', action='store_true')
+    args = ap.parse_args()
+    be = backend.get()
+    dev = be.device
+    for rows in args.rows:
+        gen = torch.Generator(device=dev).manual_seed(1)
+        pm = ParticleMesh([args.mesh] * 3, BoxSize=1.0, dtype='f8')
+        pos = torch.rand((rows, 3), generator=gen, device=dev, dtype=torch.float64)
+        probe('uniform', pm, pos, args)
+        del pos
+        torch.cuda.empty_cache()
+        if args.no_lognormal:
+            continue
+        pm = ParticleMesh([args.mesh] * 3, BoxSize=1000., dtype='f8')
+        k = numpy.geomspace(1e-3, 20.0, 200)
+        p = 2e4 * k / (1 + (k / 0.02) ** 2) ** 1.4
+        tab = Tabulated(k, numpy.sqrt(p / numpy.prod(pm.BoxSize)), loglog=True)
+        cat = lognormal_catalog(pm, tab, rows / float(numpy.prod(pm.BoxSize)), 42, bias=2.0)
+        pos = cat.pos
+        del cat
+        torch.cuda.empty_cache()
+        probe('lognormal', pm, pos, args)
+        del pos
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
