@@ -1020,6 +1020,52 @@ int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t n1, const d
                     int32_t periodic, const double *boxsize, int32_t nr, const double *e2, int32_t nsub,
                     const double *sub, int64_t *npairs, double *wnpairs, double *rsum, void *stream);
 
+/* ---- multipoles of the three-point function of particles (what nbodykit's SimulationBox3PCF does on the host with a
+ * kd-tree; pmesh_amd.threept) ------------------------------------------------------------------------------------------
+ * The rule.
+ *   rows     pos and pos2 are (n, 3) rows, float or double (a float is widened exactly), wrapped and differenced as for
+ *            the pair counts: FoF's wrap, then the minimum image of the wrapped rows.  All arithmetic is in double;
+ *            r2 = dx_0^2 + dx_1^2 + dx_2^2, summed in that order.  Three dimensions only.
+ *   bins     e2[k] = edges[k] * edges[k] is formed by the caller, edges as for the pair counts.  Row j is a neighbour of
+ *            i in bin b when e2[b] <= r2 < e2[b + 1].  A pair with r2 == 0 is never a neighbour (the row itself, a
+ *            coincident row): it has no direction.  The search radius is b = edges[nr], 2 b <= min_d L_d; nr is at most
+ *            PMX_THREEPT_MAX_BINS.
+ *   dir      r = sqrt(r2), u_d = dx_d / r.
+ *   sums     with N_i(b) the neighbours of primary i in bin b, taken from the secondaries, for l = 0 .. lmax
+ *                zeta_l[b1, b2] = sum_i w_i sum_{j in N_i(b1)} sum_{k in N_i(b2)} w_j w_k P_l(u_ij . u_ik)
+ *            the term j == k (b1 == b2) included; so that a caller can remove it: diag[b] = sum_i w_i sum_{j in N_i(b)}
+ *            w_j^2 (P_l(1) = 1: the same for every l), npairs[b] = sum_i |N_i(b)| (int64, exact), wpairs[b] = sum_i w_i
+ *            sum_{j in N_i(b)} w_j.
+ *   how      per primary A_{l,c}(b) = sum_j w_j Y_{l,c}(u_ij) over the 2 l + 1 real components, for m = 0 .. l,
+ *            Y = N_lm Q_l^m(u_z) Re / Im (u_x + i u_y)^m with N_lm = sqrt(eps_m (l - m)! / (l + m)!), eps_0 = 1, eps_m =
+ *            2 otherwise; Q_l^m = P_l^m / sin^m, a polynomial in u_z, from Q_m^m = (2 m - 1)!!, Q_{m+1}^m = (2 m + 1) z
+ *            Q_m^m and (l - m) Q_l^m = (2 l - 1) z Q_{l-1}^m - (l + m - 1) Q_{l-2}^m; (u_x + i u_y)^m by repeated
+ *            complex multiplication.  By the addition theorem sum_c A_{l,c}(b1) A_{l,c}(b2) is the double sum of P_l,
+ *            and zeta_l += w_i times it (Slepian & Eisenstein 2015: O(N neighbours), not O(N neighbours^2)).
+ *            N_00 Q_0^0 = 1 exactly: with unit weights zeta_0 is a sum of integers, exact below 2^53.
+ *   forms    the entry knows no row identity: a caller passes one set as both for the auto form.  The order of the
+ *            double sums is unspecified; npairs, and zeta_0 with unit weights, never vary. */
+#define PMX_THREEPT_MAX_ELL 10           /* the largest multipole l of one call */
+#define PMX_THREEPT_MAX_BINS 32          /* the most radial bins nr of one call */
+
+/* zeta[l, b1, b2], diag[b], wpairs[b], npairs[b] += the sums of the rule (DEVICE double (lmax + 1, nr, nr), double (nr),
+ * double (nr), int64 (nr); the caller zeroes them, or keeps adding); the sums go into zeta[l, b1 >= b2] and the entry
+ * ends by copying them to zeta[l, b2, b1]: zeta is symmetric to the last bit.  One entry, one kernel and that copy.
+ * The primaries (spos1, order1, cell_of1), the secondaries (spos2, order2, cell_start2), the weights and the grid
+ * (ncell, periodic, boxsize; three axes) are those of pmx_pair_counts; e2: DEVICE double, nr + 1 entries; lmax in
+ * 0 .. PMX_THREEPT_MAX_ELL.
+ * One workgroup takes a run of consecutive slots of the primaries and treats them one after another: its lanes stride
+ * over the slots of the 27 neighbouring cells, compact the neighbours into a chunk in LDS, evaluate w Y for a chunk
+ * at a time and add it into A[bin][component] in LDS with one owner per word; after the walk every lane adds w_i sum_c
+ * A[b1][c] A[b2][c] into the outputs (l, b1 >= b2) it keeps in registers for the whole run.  One global atomic per
+ * workgroup and non-zero output at its end.  No 32-bit counter spans more than one primary.  Reads 28 bytes per
+ * primary and 24 (+ 4 + elsize with weight2) per visited pair, the latter from cache. */
+int pmx_threept_multipoles(int64_t n1, const double *spos1, const int32_t *order1, const int32_t *cell_of1,
+                           const pmx_vec *weight1, int64_t n2, const double *spos2, const int32_t *order2,
+                           const int32_t *cell_start2, const pmx_vec *weight2, const int64_t *ncell, int32_t periodic,
+                           const double *boxsize, int32_t nr, const double *e2, int32_t lmax, double *zeta,
+                           double *diag, double *wpairs, int64_t *npairs, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

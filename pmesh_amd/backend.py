@@ -507,6 +507,20 @@ class HipBackend(object):
                   sub.data_ptr() if sub is not None else None, npairs.data_ptr(), wnpairs.data_ptr(), rsum.data_ptr(),
                   self.stream())
 
+    def threept_multipoles(self, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2, ncell,
+                           periodic, boxsize, e2, lmax, zeta, diag, wpairs, npairs):
+        """the sums of the three-point multipoles of the primaries with the secondaries (as in pair_counts, three
+        columns) added into the zeroed tensors `zeta` (float64, (lmax + 1, nr, nr)), `diag`, `wpairs` (float64, nr) and
+        `npairs` (int64, nr).  e2: the nr + 1 squared edges on the device (pmx_threept_multipoles)"""
+        if spos1.shape[0] == 0 or spos2.shape[0] == 0:
+            return
+        wv1, wv2 = _arrays.vec(weight1), _arrays.vec(weight2)
+        self.call('threept_multipoles', spos1.shape[0], spos1.data_ptr(), order1.data_ptr(), cell_of1.data_ptr(),
+                  C.byref(wv1) if weight1 is not None else None, spos2.shape[0], spos2.data_ptr(), order2.data_ptr(),
+                  cell_start2.data_ptr(), C.byref(wv2) if weight2 is not None else None, _abi.i64arr(ncell, 3),
+                  int(periodic), _abi.f64arr(boxsize, 3), e2.numel() - 1, e2.data_ptr(), int(lmax), zeta.data_ptr(),
+                  diag.data_ptr(), wpairs.data_ptr(), npairs.data_ptr(), self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""

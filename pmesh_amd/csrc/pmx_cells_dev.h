@@ -77,6 +77,33 @@ __device__ __forceinline__ bool fof_neighbour(const FGeom &g, const int32_t c[3]
 
 template <int NDIM> constexpr int fof_neighbours() { return NDIM == 1 ? 3 : (NDIM == 2 ? 9 : 27); }
 
+// the bins of an axis: up to this many are searched by a linear walk from the outermost, more by bisection
+constexpr int PAIRS_LINEAR = 8;
+
+// the minimum image of dx = w - w', both in [0, L): fof_image without its division where the quotient is known.
+// |dx| <= L / 4 (exact: a power of two times L) gives |dx / L| <= 1/4 after rounding, rint of it 0, and dx - L * 0 = dx.
+__device__ __forceinline__ double pair_image(double dx, double L, double quarter)
+{
+    return fabs(dx) <= quarter ? dx : fof_image(dx, L);
+}
+
+// the largest k in 0 .. n - 1 with q >= tab[k], given q >= tab[0]; tab increasing
+template <typename P> __device__ __forceinline__ int pair_bin(P tab, int n, double q)
+{
+    if (n <= PAIRS_LINEAR) {
+        int k = n - 1;
+        while (k > 0 && q < tab[k]) k--;
+        return k;
+    }
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (q >= tab[mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // the grid of a launch, checked (origin and inv_side may be NULL for the passes that only walk cells)
 static inline int fof_geom(int32_t ndim, const double *boxsize, const double *origin, const double *inv_side,
                            const int64_t *ncell, int32_t periodic, FGeom &g, int64_t *ncells)

@@ -30,7 +30,6 @@ constexpr int PBLOCK = 256;
 constexpr int PAIRS_SLOTS_SMALL = 1024;          // the bins of the histogram of the small form: 12 / 20 KB
 constexpr int PAIRS_SLOTS_BIG = PMX_PAIRS_MAX_BINS;   // of the form for many bins: 48 / 80 KB, two workgroups per CU
 constexpr int PAIRS_EDGES_LDS = 128;             // up to this many bins along an axis, its edges are searched in LDS
-constexpr int PAIRS_LINEAR = 8;                  // up to this many, by a linear walk from the outermost
 // the secondaries of one launch: 256 lanes x 2^23 slots = 2^31 pairs at most per workgroup and 32-bit count
 constexpr int64_t PAIRS_WINDOW = (int64_t)1 << 23;
 
@@ -47,30 +46,6 @@ struct PArgs {
     unsigned long long *npairs;
     double *wnpairs, *rsum;
 };
-
-// the minimum image of dx = w - w', both in [0, L): fof_image without its division where the quotient is known.
-// |dx| <= L / 4 (exact: a power of two times L) gives |dx / L| <= 1/4 after rounding, rint of it 0, and dx - L * 0 = dx.
-__device__ __forceinline__ double pair_image(double dx, double L, double quarter)
-{
-    return fabs(dx) <= quarter ? dx : fof_image(dx, L);
-}
-
-// the largest k in 0 .. n - 1 with q >= tab[k], given q >= tab[0]; tab increasing
-template <typename P> __device__ __forceinline__ int pair_bin(P tab, int n, double q)
-{
-    if (n <= PAIRS_LINEAR) {
-        int k = n - 1;
-        while (k > 0 && q < tab[k]) k--;
-        return k;
-    }
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (q >= tab[mid]) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // the number of k in 1 .. n - 1 with z2 >= tab[k] * r2 (the products do not decrease with k: the test holds for a
 // prefix of them)
