@@ -1066,6 +1066,42 @@ int pmx_threept_multipoles(int64_t n1, const double *spos1, const int32_t *order
                            const double *boxsize, int32_t nr, const double *e2, int32_t lmax, double *zeta,
                            double *diag, double *wpairs, int64_t *npairs, void *stream);
 
+/* ---- the short-range pair force of particles (the tree half of MP-Gadget's TreePM force, as a P3M sum over the cell
+ * grid; pmesh_amd.shortrange) ---------------------------------------------------------------------------------------
+ * The rule.
+ *   rows     pos (primaries) and pos2 (sources) are (n, 3) rows, float or double (a float is widened exactly), wrapped
+ *            and differenced as for the pair counts: FoF's wrap, then dx_d = x_i,d - x_j,d, the minimum image of the
+ *            wrapped rows.  All arithmetic is in double; r2 = dx_0^2 + dx_1^2 + dx_2^2, summed in that order.  Three
+ *            dimensions only.
+ *   cut      source j is a neighbour of primary i when 0 < r2 < rc2, rc2 = r_cut * r_cut formed by the caller; no
+ *            square root decides it.  r_cut is finite, positive and 2 r_cut <= min_d L_d.  A pair with r2 == 0 (a row
+ *            with itself, coincident rows) contributes nothing: the entry needs no row identity, and a caller that
+ *            passes one set as both has nothing to correct.
+ *   force    r = sqrt(r2), u = r / (2 r_split), s2 = r2 + eps2 (eps2 = softening^2, Plummer),
+ *                fac = erfc(u) + (2 / sqrt(pi)) u exp(-u^2)
+ *                acc_i,d = -G sum_j m_j dx_d fac / (s2 sqrt(s2))
+ *                pot_i   = -G sum_j m_j erfc(u) / sqrt(s2)
+ *                neighbours_i = the number of neighbours (int64, exact)
+ *            erfc and exp are the device's double functions, evaluated in closed form for every pair.  The sum of this
+ *            force and a mesh force filtered by exp(-k^2 r_split^2) (pmx_transfer.gauss_r = sqrt(2) r_split) is
+ *            Newton's.
+ *   sums     the order of the double sums is unspecified: their last bits may vary; neighbours never varies. */
+
+/* acc[i, :], pot[i], neighbours[i] = the sums of the rule for row i of the primaries (DEVICE double (n1, 3), double
+ * (n1) or NULL, int64 (n1) or NULL), in ROW order (written through order1); they are overwritten, not added to.
+ * The primaries (spos1, order1, cell_of1), the sources (spos2, order2, cell_start2) and the grid (ncell, periodic,
+ * boxsize; three axes) are those of pmx_pair_counts; the same arrays may be passed for both sets.  mass2: one column of
+ * n2 floats or doubles in ROW order (read through order2), NULL for 1.  G, r_split > 0, rc2 > 0 and eps2 >= 0 are
+ * finite.  One entry, one kernel: one wave per slot of the primaries strides over the slots of the 27 neighbouring
+ * cells, compacts the pairs inside the cut into a ring in LDS of its own and evaluates the force 64 pairs at a time;
+ * a fixed shuffle tree sums the lanes.  No atomics, no counter that spans more than one primary.  Reads 28 bytes and
+ * writes 24 (+ 8 + 8) per primary, reads 24 per visited pair (+ 4 + elsize per neighbour with masses), the latter from
+ * cache. */
+int pmx_short_range(int64_t n1, const double *spos1, const int32_t *order1, const int32_t *cell_of1, int64_t n2,
+                    const double *spos2, const int32_t *order2, const int32_t *cell_start2, const pmx_vec *mass2,
+                    const int64_t *ncell, int32_t periodic, const double *boxsize, double G, double r_split,
+                    double rc2, double eps2, double *acc, double *pot, int64_t *neighbours, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

@@ -521,6 +521,22 @@ class HipBackend(object):
                   int(periodic), _abi.f64arr(boxsize, 3), e2.numel() - 1, e2.data_ptr(), int(lmax), zeta.data_ptr(),
                   diag.data_ptr(), wpairs.data_ptr(), npairs.data_ptr(), self.stream())
 
+    def short_range(self, spos1, order1, cell_of1, spos2, order2, cell_start2, mass2, ncell, periodic, boxsize, G,
+                    r_split, rc2, eps2, acc, pot=None, neighbours=None):
+        """the short-range pair force of the primaries from the sources (as in pair_counts, three columns) written to
+        the rows of `acc` (float64, (n1, 3)), `pot` (float64, n1) and `neighbours` (int64, n1), the last two or None,
+        in row order: overwritten, not added to.  mass2: an (n2,) or (n2, 1) float tensor in row order, or None
+        (pmx_short_range)"""
+        if spos1.shape[0] == 0:
+            return
+        mv = _arrays.vec(mass2)
+        self.call('short_range', spos1.shape[0], spos1.data_ptr(), order1.data_ptr(), cell_of1.data_ptr(),
+                  spos2.shape[0], spos2.data_ptr(), order2.data_ptr(), cell_start2.data_ptr(),
+                  C.byref(mv) if mass2 is not None else None, _abi.i64arr(ncell, 3), int(periodic),
+                  _abi.f64arr(boxsize, 3), float(G), float(r_split), float(rc2), float(eps2), acc.data_ptr(),
+                  pot.data_ptr() if pot is not None else None,
+                  neighbours.data_ptr() if neighbours is not None else None, self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""

@@ -49,6 +49,11 @@ class Transfer(object):
         return cls(laplace_pow=-1, grad_dir=direction, grad_kind='finite4')
 
     @classmethod
+    def long_range(cls, direction, r_split, grad_kind='finite4'):
+        """ 1j * D(k_d) / k^2 * exp(-k^2 r_split^2): the mesh partner of shortrange.short_range_force(r_split) """
+        return cls(laplace_pow=-1, grad_dir=direction, grad_kind=grad_kind, gauss_r=numpy.sqrt(2.0) * r_split)
+
+    @classmethod
     def potential(cls):
         """ -1 / k^2  (examples/nbody.py:173-176; transfer.py:232-240) """
         return cls(amplitude=-1.0, laplace_pow=-1)
