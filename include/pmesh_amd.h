@@ -1102,6 +1102,46 @@ int pmx_short_range(int64_t n1, const double *spos1, const int32_t *order1, cons
                     const int64_t *ncell, int32_t periodic, const double *boxsize, double G, double r_split,
                     double rc2, double eps2, double *acc, double *pot, int64_t *neighbours, void *stream);
 
+/* ---- the k nearest neighbours of particles (what callers do with a kd-tree on the host: nbodykit's KDDensity,
+ * MP-Gadget's smoothing lengths, the kNN-CDF statistics; pmesh_amd.knn) -----------------------------------------------
+ * The rule.
+ *   rows        pos (primaries) and pos2 (sources) are (n, ndim) rows, ndim = 1, 2 or 3, float or double (a float is
+ *               widened exactly), wrapped and differenced as for the pair counts: FoF's wrap, then dx_d = x_i,d - x_j,d,
+ *               the minimum image of the wrapped rows.  All arithmetic is in double, every operation rounded once; r2 =
+ *               sum_d dx_d^2, accumulated in the order d = 0, 1, 2.
+ *   candidates  source j is a candidate of primary i when r2 < rmax2, rmax2 = rmax * rmax formed by the caller; no
+ *               square root decides anything.  rmax is finite, positive and 2 rmax <= min_d L_d.
+ *   result      dist2[i, :] are the k smallest candidate r2 of row i, ascending, +inf where there are fewer candidates.
+ *               The multiset of the k smallest values is unique: dist2 is defined bit for bit and depends on no
+ *               decomposition, launch or search schedule.  index[i, c] is a source whose r2 to row i equals dist2[i, c],
+ *               -1 where that is inf; the indices of a row are distinct; among sources tied in r2 the one named is
+ *               unspecified: the indices are witnesses, not a canonical order.  found[i] is the number of finite
+ *               columns.
+ *   auto form   the entry knows no row identity: a caller that searches a set in itself asks for k + 1 and removes the
+ *               column that names the row itself (r2 == 0 exactly), or the last column where it is not named. */
+#define PMX_KNN_MAX_K 64                 /* the most neighbours k of one call: one per lane of a wave */
+
+/* dist2[i, :], index[i, :], count[i] = the k smallest r2 < r2max of row i of the primaries, ascending and padded with
+ * +inf; the LOCAL rows of those sources (through order2), -1 where inf; the exact number of sources with r2 < r2max,
+ * not capped at k (DEVICE double (n1, k), int32 (n1, k) or NULL, int64 (n1) or NULL), in ROW order (written through
+ * order1); they are overwritten.  One launch is a fixed-radius top-k over the 3^ndim neighbouring cells: r2max is the
+ * squared radius of this launch, and the cells have a side of at least that radius.  count[i] >= k says that the k
+ * nearest of row i all lie inside the radius; a caller that wants the k nearest within a larger rmax launches again
+ * with a larger radius for the other rows (pmesh_amd.knn.knn: the radius doubles).
+ * The primaries (spos1, order1, cell_of1), the sources (spos2, order2, cell_start2) and the grid (ncell, periodic,
+ * boxsize; ndim axes) are those of pmx_pair_counts; the same arrays may be passed for both sets.  1 <= k <=
+ * PMX_KNN_MAX_K.  One entry, one kernel: one wave per slot of the primaries strides over the slots of the neighbouring
+ * cells; count is the sum of the ballots' populations; a candidate is kept when r2 < tau, tau = r2max until the wave's
+ * list holds k finite entries and their k-th smallest from then on; what is kept is compacted into a ring in LDS of the
+ * wave's own and merged 64 entries at a time into the best list (one entry per lane, ascending) by a bitonic sort, a
+ * min with the reversed list and a bitonic merge, all lane exchanges.  No atomics, no counter that spans more than one
+ * primary.  Reads 4 + 4 + 8 ndim bytes and writes 12 k + 8 per primary, reads 8 ndim per visited source, the latter
+ * from cache. */
+int pmx_knn(int32_t ndim, int64_t n1, const double *spos1, const int32_t *order1, const int32_t *cell_of1, int64_t n2,
+            const double *spos2, const int32_t *order2, const int32_t *cell_start2, const int64_t *ncell,
+            int32_t periodic, const double *boxsize, double r2max, int32_t k, double *dist2, int32_t *index,
+            int64_t *count, void *stream);
+
 /* Where the master seed stream of pmx_whitenoise runs (pmesh/_whitenoise_generics.h:73-93: one RANLUX stream walked in
  * rings over the (i, j) plane, one seed per column): 0 (default) one host core + a copy of 8 bytes per local column;
  * 1 one device thread (no copy, no wait; a sequential chain: ~35 x slower than the host core).  Same tables bit for bit. */

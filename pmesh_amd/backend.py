@@ -537,6 +537,20 @@ class HipBackend(object):
                   pot.data_ptr() if pot is not None else None,
                   neighbours.data_ptr() if neighbours is not None else None, self.stream())
 
+    def knn(self, spos1, order1, cell_of1, spos2, order2, cell_start2, ncell, periodic, boxsize, r2max, k, dist2,
+            index=None, count=None):
+        """the k smallest r2 < r2max of the primaries among the sources (as in pair_counts, ndim columns) written to
+        the rows of `dist2` (float64, (n1, k), ascending, +inf where there are fewer), the local source rows to `index`
+        (int32, (n1, k), -1 where inf) and the number of sources with r2 < r2max to `count` (int64, n1), the last two
+        or None, in row order: overwritten (pmx_knn)"""
+        if spos1.shape[0] == 0:
+            return
+        self.call('knn', spos1.shape[1], spos1.shape[0], spos1.data_ptr(), order1.data_ptr(), cell_of1.data_ptr(),
+                  spos2.shape[0], spos2.data_ptr(), order2.data_ptr(), cell_start2.data_ptr(), _abi.i64arr(ncell, 3),
+                  int(periodic), _abi.f64arr(boxsize, 3), float(r2max), int(k), dist2.data_ptr(),
+                  index.data_ptr() if index is not None else None,
+                  count.data_ptr() if count is not None else None, self.stream())
+
     def lpt_hessian(self, v, pairs, outs, start, nmesh, boxsize):
         """outs[p] = k_i k_j / k^2 v for (i, j) = pairs[p], 1-3 outputs, over the local complex block v
         (pmx_lpt_hessian)"""
