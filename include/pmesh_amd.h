@@ -16,8 +16,25 @@
  *    (libpmesh_amd.so).  The test oracle (oracle/liboracle.so) exports the
  *    same signatures with the prefix pmo_ and HOST pointers.
  *  - strides are in BYTES (as numpy strides; pmesh/_window.pyx:152-154).
- *  - `stream` is a hipStream_t passed as void* (NULL = default stream).  Calls
- *    are asynchronous with respect to the host unless stated otherwise.
+ *  - `stream` is a hipStream_t passed as void* (NULL = default stream).  Every kernel,
+ *    copy and fill of an entry is enqueued on that stream, in order, and on no other.
+ *    Calls are asynchronous with respect to the host unless stated otherwise.  Stated
+ *    otherwise, here in one place (tests/test_streams.py holds both promises for every
+ *    entry that takes `stream`):
+ *      pmx_whitenoise         waits for the stream before it returns while the master seed stream runs on the host
+ *                             (the default, pmx_whitenoise_master(0)): the seed tables it copies are its own.
+ *      pmx_binplan_build      waits once in the life of a plan object: a build of 2^16 rows or more with the
+ *                             tile-ordered copy left to the library (pmx_binplan_sorted -1) on a plan that has not yet
+ *                             measured the coherence of about as many rows reads that measurement back.
+ *      first calls            an entry that grows a pooled buffer frees the old one (hipFree waits for the device) and
+ *                             allocates: the buffers of a bin plan (pmx_binplan_build, pmx_paint_binned[_defer],
+ *                             pmx_readout_binned[_multi], pmx_binplan_order) when the batch or the block outgrows them, the
+ *                             chunk tables of pmx_decompose_count / _fill; and the first LDS transform of a length and
+ *                             precision on a device (pmx_colfft*, pmx_rowfft*) and the first finite-difference transfer of
+ *                             a mesh and box side copy a table from the host synchronously.  Warm, none of them waits.
+ *    The entries without a stream (pmx_fft_create / _destroy, pmx_binplan_create / _destroy, pmx_window_set_table and
+ *    the settings) are host calls; pmx_window_set_table copies synchronously.  A plan object (pmx_binplan, pmx_fft)
+ *    is mutable state: its calls belong on one stream at a time.
  *  - every function returns a pmx_status; pmx_last_error() gives the message.
  */
 #ifndef PMESH_AMD_H
@@ -230,8 +247,9 @@ int pmx_binplan_builds(pmx_binplan *plan, uint32_t *single_pass, uint32_t *two_p
  * history that gave the entry form up (from two on the plan keeps the list).  Host state only: no synchronisation. */
 int pmx_binplan_blocks(pmx_binplan *plan, int32_t *in_entry_form, uint32_t *drops);
 /* [r6] The order of the rows that a built plan holds, for the caller: order[k] (npart int64 of device memory) = the row that
- * stands k-th when the rows are taken tile by tile — inside a tile in the order of the rows themselves — and the rows
- * that touch no local cell last.  A time-stepping caller re-sorts its particle arrays with it every few steps
+ * stands k-th when the rows are taken tile by tile — inside a tile in the order of the plan's list, which is not that
+ * of the rows and changes from build to build (tests/stream_cases.py: TileOrder) — and the rows that touch no local cell
+ * last.  A time-stepping caller re-sorts its particle arrays with it every few steps
  * (ParticleMesh.tile_order; the reference has no counterpart): position gathers and result stores of the tile kernels
  * then touch whole lines again, whatever the flow has done to the order the particles were made in. */
 int pmx_binplan_order(pmx_binplan *plan, int64_t *order, void *stream);

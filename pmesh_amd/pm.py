@@ -1469,7 +1469,8 @@ class ParticleMesh(object):
                 o = pm.tile_order(pos);  pos = pos[o];  vel = vel[o];  ...
 
             restores it.  The order is tile by tile (8 x 16 x 32 cells, C order of the tiles of this
-            rank's block); INSIDE a tile the rows keep the order they had — sorting them by cell as
+            rank's block); INSIDE a tile the rows are not sorted by cell (on the device they stand in the
+            order of the bin plan's list, which changes from build to build) — sorting them by cell as
             well would put the particles of a crowded cell into neighbouring lanes of the paint
             kernel, the worst case of its LDS atomics (measured on an evolved 512^3 state: paint 4.2 ms
             cell-sorted against 2.2 as the run left the rows and 1.4 in random order; the readout

@@ -157,7 +157,10 @@ def expected(field, kedges, other=None, muedges=None, los=None, poles=(), deconv
                        acc, list(poles))
 
 
-def assert_same(got, want, rtol=1e-12):
+RTOL = 1e-12          # of the scale of a column: the bound of every comparison of binned spectra with their restatement
+
+
+def assert_same(got, want, rtol=RTOL):
     assert (got.modes == want.modes).all(), numpy.nonzero(got.modes != want.modes)
 
     def close(x, y, scale=None):
