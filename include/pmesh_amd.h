@@ -1011,11 +1011,36 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *            in bin (0, 0) when edges[0] == 0 and nowhere otherwise.
  *   sums     per bin: npairs (int64, exact); wnpairs = sum w1_i w2_j (double); rsum = sum w1_i w2_j sqrt(q) (double).
  *            The order of the double sums is unspecified: their last bits may differ from run to run; npairs never does.
- * The bin of a pair is r-bin * nsub + sub-bin (nsub = 1 in the mode 1D); nr * nsub <= PMX_PAIRS_MAX_BINS. */
+ * The bin of a pair is r-bin * nsub + sub-bin (nsub = 1 in the mode 1D); nr * nsub <= PMX_PAIRS_MAX_BINS.
+ *
+ * The modes with the line of sight of the pair itself (what nbodykit's SurveyDataPairCount does on the host with
+ * Corrfunc's DDsmu_mocks / DDrppi_mocks; pmesh_amd.surveypairs).  Rows, edges, pairs and sums are as above; the new
+ * parts:
+ *   observer  the entry knows one observer, the centre of the box: o_d = L_d / 2.  For a pair of wrapped rows w_i, w_j:
+ *             dx_d as above; l_d = (w_i,d + w_j,d) - L_d, two roundings: twice the offset of the pair's midpoint from the
+ *             observer, of which only the direction matters.  p = dx_0 l_0 + dx_1 l_1 + dx_2 l_2, l2 = l_0^2 + l_1^2 +
+ *             l_2^2, r2 = dx_0^2 + dx_1^2 + dx_2^2, each sum taken in that order; p2 = p * p.
+ *   PMX_PAIRS_2D_MIDPOINT, bins of (s, mu): the r-bin comes from q = r2 as in the mode 2D.  t = r2 * l2; the mu-bin is
+ *             the number of k in 1 .. nsub - 1 with p2 >= sub[k] * t, sub[k] = muedges[k]^2: no division.  A pair with
+ *             t == 0 goes to mu-bin 0: r2 == 0, and a pair symmetric about the observer.  Corrfunc's DDsmu_mocks:
+ *             mu^2 = (s.l)^2 / (s^2 l^2), l = (x1 + x2) / 2.
+ *   PMX_PAIRS_PROJECTED_MIDPOINT, bins of (rp, pi): pi2 = p2 / l2, or 0 where l2 == 0; rp2 = r2 - pi2, or 0 where that
+ *             is negative.  The r-bin comes from q = rp2 against e2.  sub[k] = piedges[k]^2 (squared by the caller,
+ *             unlike PMX_PAIRS_PROJECTED, which takes piedges themselves); the pi-bin is the number of k in
+ *             1 .. nsub - 1 with pi2 >= sub[k]; a pair with pi2 >= sub[nsub] is not counted.  rsum adds w sqrt(rp2).
+ *             Corrfunc's DDrppi_mocks: pi = |s.l| / |l|, rp^2 = s^2 - pi^2.
+ *   both      los is ignored; ndim == 3; both are symmetric under exchanging the two rows, so one set passed as both
+ *             still counts every unordered pair twice.  The grid, the wrapping and the minimum image stay periodic: a
+ *             caller with a survey keeps every row in [b / 2, L_d - b / 2), b the search radius (edges[nr]; in the
+ *             projected mode hypot(edges[nr], piedges[nsub]): the walk over the cells must cover the bounding sphere of
+ *             the cylinder), so that no two rows are closer than b through the boundary and no counted pair is a
+ *             wrapped one. */
 #define PMX_PAIRS_MAX_BINS 4096          /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
 #define PMX_PAIRS_PROJECTED 2            /* bins of (rp, pi) */
+#define PMX_PAIRS_2D_MIDPOINT 3          /* bins of (s, mu), the line of sight from the box centre to the pair's midpoint */
+#define PMX_PAIRS_PROJECTED_MIDPOINT 4   /* bins of (rp, pi), the same line of sight */
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
@@ -1026,8 +1051,9 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * needed: one lane per slot of the primaries walks the 3^ndim neighbouring cells of its row in the secondaries.
  * weight1 / weight2: one column of n1 / n2 floats or doubles in ROW order (read through order1 / order2), NULL for 1.
  * With both NULL no weight is read and wnpairs[b] += (double)(the count).
- * e2: DEVICE double, nr + 1 entries.  sub: DEVICE double, nsub + 1 entries, m2 (2D) or piedges (projected); NULL and
- * nsub = 1 in the mode 1D.  los is ignored in the mode 1D.
+ * e2: DEVICE double, nr + 1 entries.  sub: DEVICE double, nsub + 1 entries, m2 (2D, 2D_MIDPOINT), piedges (projected)
+ * or piedges^2 (PROJECTED_MIDPOINT); NULL and nsub = 1 in the mode 1D.  los is ignored in the mode 1D and in the two
+ * midpoint modes, whose kernels (pmx_pairs_survey.hip) are launched from this entry like the others.
  * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
  * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
  * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)

@@ -14,6 +14,8 @@
     from pmesh_amd.mock import poisson_sample, lognormal_catalog   # particles Poisson-sampled from a field; lognormal mocks
     from pmesh_amd.fof import fof, fof_catalog                     # friends-of-friends groups and a halo catalogue
     from pmesh_amd.paircount import pair_counts, pair_correlation   # binned pair counts and xi(r), xi(r, mu), xi(rp, pi)
+    from pmesh_amd.surveypairs import survey_pair_counts, survey_correlation   # xi(s, mu), wp(rp), w(theta) of a survey: pairwise line of sight
+    from pmesh_amd.surveypairs import to_poles, to_wp, sky_to_cartesian   # and what goes with them
     from pmesh_amd.threept import threept_multipoles, threept_correlation   # three-point multipoles zeta_l(r1, r2) of particles
     from pmesh_amd.shortrange import short_range_force              # the short-range pair force of a TreePM / P3M split
     from pmesh_amd.knn import knn, knn_density, knn_cdf             # k-nearest-neighbour distances, densities and the kNN-CDF

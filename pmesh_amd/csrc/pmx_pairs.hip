@@ -17,48 +17,12 @@
 // at its end the workgroup makes one global atomic per array and non-zero bin.  (Replicating the histogram over the
 // lanes, slot = bin * R + lane % R, so that the lanes of a wave that meet in one outer bin do not meet on one address,
 // measured nothing at 20 bins, and neither did removing the LDS atomics altogether: DESIGN.md 5.7.)  No lane waits for
-// another: the only barriers are the two around the walk.
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "pmx_cells_dev.h"
-#include "pmx_common.h"
+// another: the only barriers are the two around the walk.  The histogram, the walk and the arguments are those of
+// pmx_pairs_dev.h; the modes whose line of sight is the pair's own (PMX_PAIRS_2D_MIDPOINT, PMX_PAIRS_PROJECTED_MIDPOINT)
+// have their kernels in pmx_pairs_survey.hip and are launched from pmx_pair_counts below.
+#include "pmx_pairs_dev.h"
 
 namespace pmx {
-
-constexpr int PBLOCK = 256;
-constexpr int PAIRS_SLOTS_SMALL = 1024;          // the bins of the histogram of the small form: 12 / 20 KB
-constexpr int PAIRS_SLOTS_BIG = PMX_PAIRS_MAX_BINS;   // of the form for many bins: 48 / 80 KB, two workgroups per CU
-constexpr int PAIRS_EDGES_LDS = 128;             // up to this many bins along an axis, its edges are searched in LDS
-// the secondaries of one launch: 256 lanes x 2^23 slots = 2^31 pairs at most per workgroup and 32-bit count
-constexpr int64_t PAIRS_WINDOW = (int64_t)1 << 23;
-
-struct PArgs {
-    FGeom g;
-    int64_t n1, n2;
-    int32_t slo, shi;                            // the slots of the secondaries of this launch
-    const double *spos1, *spos2;
-    const int32_t *order1, *cell_of1, *order2, *cell_start2;
-    DVec w1, w2;
-    int64_t ncells;
-    int32_t nr, nsub, nbins, los;
-    const double *e2, *sub;
-    unsigned long long *npairs;
-    double *wnpairs, *rsum;
-};
-
-// the number of k in 1 .. n - 1 with z2 >= tab[k] * r2 (the products do not decrease with k: the test holds for a
-// prefix of them)
-template <typename P> __device__ __forceinline__ int pair_mu_bin(P tab, int n, double z2, double r2)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (z2 >= tab[mid] * r2) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 template <int NDIM, int MODE, bool WEIGHTED, int SLOTS>
 __global__ void __launch_bounds__(PBLOCK) pairs_kernel(PArgs a)
@@ -66,29 +30,20 @@ __global__ void __launch_bounds__(PBLOCK) pairs_kernel(PArgs a)
     __shared__ uint32_t hcount[SLOTS];
     __shared__ double hrsum[SLOTS];
     __shared__ double hwsum[WEIGHTED ? SLOTS : 1];
-    // (the weighted form for many bins fills its 80 KB with the histogram: it searches the edges in global memory)
-    constexpr int EL = WEIGHTED && SLOTS > PAIRS_SLOTS_SMALL ? 0 : PAIRS_EDGES_LDS;
+    constexpr int EL = pair_edges_lds<WEIGHTED, SLOTS>();
     __shared__ double se2[EL + 1];
     __shared__ double ssub[MODE == PMX_PAIRS_1D ? 1 : EL + 1];
     const int tid = threadIdx.x;
     const int used = min(a.nbins, SLOTS);
-    for (int s = tid; s < used; s += PBLOCK) {
-        hcount[s] = 0;
-        hrsum[s] = 0;
-        if (WEIGHTED) hwsum[s] = 0;
-    }
+    pair_hist_zero<WEIGHTED>(hcount, hrsum, hwsum, used, tid);
     const bool e_lds = EL > 0 && a.nr <= EL, s_lds = EL > 0 && a.nsub <= EL;
-    if (e_lds)
-        for (int s = tid; s <= a.nr; s += PBLOCK) se2[s] = a.e2[s];
-    if (MODE != PMX_PAIRS_1D && s_lds)
-        for (int s = tid; s <= a.nsub; s += PBLOCK) ssub[s] = a.sub[s];
+    if (e_lds) pair_edges_load(se2, a.e2, a.nr, tid);
+    if (MODE != PMX_PAIRS_1D && s_lds) pair_edges_load(ssub, a.sub, a.nsub, tid);
     __syncthreads();
 
     const int64_t k = (int64_t)blockIdx.x * PBLOCK + tid;
-    int32_t i = -1, flat = -1;
-    if (k < a.n1) i = a.order1[k];
-    if (i >= 0 && i < a.n1) flat = a.cell_of1[i];               // (always, with the order fill_kernel left)
-    if (flat >= 0 && flat < a.ncells) {
+    int32_t i, flat;
+    if (pair_primary(a, k, i, flat)) {
         const FGeom &g = a.g;
         double x[NDIM], quarter[NDIM];
 #pragma unroll
@@ -102,68 +57,37 @@ __global__ void __launch_bounds__(PBLOCK) pairs_kernel(PArgs a)
         const double pimax = MODE == PMX_PAIRS_PROJECTED ? a.sub[a.nsub] : 0.0;
         int32_t c[3];
         fof_cell_axes<NDIM>(g, flat, c);
-        for (int nb = 0; nb < fof_neighbours<NDIM>(); nb++) {
-            int32_t cell;
-            if (!fof_neighbour<NDIM>(g, c, nb, cell)) continue;
-            const int32_t s0 = max(a.cell_start2[cell], a.slo), s1 = min(a.cell_start2[cell + 1], a.shi);
-            for (int32_t s = s0; s < s1; s++) {
-                double dx[3] = {0, 0, 0};
+        pair_walk<NDIM>(a, c, x, quarter, [&](int32_t s, const double *, const double *dx) {
+            double q = 0, z = 0;
+            if (MODE == PMX_PAIRS_PROJECTED) {
 #pragma unroll
                 for (int d = 0; d < NDIM; d++)
-                    dx[d] = pair_image(x[d] - a.spos2[(int64_t)s * NDIM + d], g.L[d], quarter[d]);
-                double q = 0, z = 0;
-                if (MODE == PMX_PAIRS_PROJECTED) {
+                    if (d != a.los) q += dx[d] * dx[d];
+            } else {
 #pragma unroll
-                    for (int d = 0; d < NDIM; d++)
-                        if (d != a.los) q += dx[d] * dx[d];
-                } else {
-#pragma unroll
-                    for (int d = 0; d < NDIM; d++) q += dx[d] * dx[d];
-                }
-                if (!(q >= qlo && q < qhi)) continue;
-                if (MODE != PMX_PAIRS_1D) z = a.los == 0 ? dx[0] : (a.los == 1 ? dx[1] : dx[2]);
-                int bin = e_lds ? pair_bin(se2, a.nr, q) : pair_bin(a.e2, a.nr, q);
-                if (MODE == PMX_PAIRS_2D) {
-                    const double z2 = z * z;
-                    int m = 0;
-                    if (q > 0) m = s_lds ? pair_mu_bin(ssub, a.nsub, z2, q) : pair_mu_bin(a.sub, a.nsub, z2, q);
-                    bin = bin * a.nsub + m;
-                }
-                if (MODE == PMX_PAIRS_PROJECTED) {
-                    const double az = fabs(z);
-                    if (!(az < pimax)) continue;
-                    // (az >= 0 = piedges[0] where the edges are the rule's; anything below the first edge goes to bin 0)
-                    bin = bin * a.nsub + (s_lds ? pair_bin(ssub, a.nsub, az) : pair_bin(a.sub, a.nsub, az));
-                }
-                const int slot = bin;
-                if (slot < 0 || slot >= used) continue;            // (never: 0 <= bin < nbins)
-                const double r = sqrt(q);
-                if (WEIGHTED) {
-                    double w = w1;
-                    if (a.w2.data) {
-                        const int32_t j = a.order2[s];
-                        if (j < 0 || j >= a.n2) continue;          // (never, with the order fill_kernel left)
-                        w = w1 * a.w2.get(j, 0);
-                    }
-                    atomicAdd(&hcount[slot], 1u);
-                    atomicAdd(&hwsum[slot], w);
-                    atomicAdd(&hrsum[slot], w * r);
-                } else {
-                    atomicAdd(&hcount[slot], 1u);
-                    atomicAdd(&hrsum[slot], r);
-                }
+                for (int d = 0; d < NDIM; d++) q += dx[d] * dx[d];
             }
-        }
+            if (!(q >= qlo && q < qhi)) return;
+            if (MODE != PMX_PAIRS_1D) z = a.los == 0 ? dx[0] : (a.los == 1 ? dx[1] : dx[2]);
+            int bin = e_lds ? pair_bin(se2, a.nr, q) : pair_bin(a.e2, a.nr, q);
+            if (MODE == PMX_PAIRS_2D) {
+                const double z2 = z * z;
+                int m = 0;
+                if (q > 0) m = s_lds ? pair_mu_bin(ssub, a.nsub, z2, q) : pair_mu_bin(a.sub, a.nsub, z2, q);
+                bin = bin * a.nsub + m;
+            }
+            if (MODE == PMX_PAIRS_PROJECTED) {
+                const double az = fabs(z);
+                if (!(az < pimax)) return;
+                // (az >= 0 = piedges[0] where the edges are the rule's; anything below the first edge goes to bin 0)
+                bin = bin * a.nsub + (s_lds ? pair_bin(ssub, a.nsub, az) : pair_bin(a.sub, a.nsub, az));
+            }
+            if (bin < 0 || bin >= used) return;                    // (never: 0 <= bin < nbins)
+            pair_hist_add<WEIGHTED>(a, hcount, hrsum, hwsum, bin, s, w1, sqrt(q));
+        });
     }
     __syncthreads();
-
-    for (int b = tid; b < used; b += PBLOCK) {
-        const unsigned long long n = hcount[b];
-        if (n == 0) continue;
-        atomicAdd(&a.npairs[b], n);
-        atomicAdd(&a.wnpairs[b], WEIGHTED ? hwsum[b] : (double)n);
-        atomicAdd(&a.rsum[b], hrsum[b]);
-    }
+    pair_hist_flush<WEIGHTED>(a, hcount, hrsum, hwsum, used, tid);
 }
 
 }  // namespace pmx
@@ -189,9 +113,12 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     PArgs a;
     const int rc = fof_geom(ndim, boxsize, nullptr, nullptr, ncell, periodic, a.g, &a.ncells);
     if (rc != PMX_OK) return rc;
-    PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED, PMX_EINVAL, "bad mode");
-    PMX_REQUIRE(mode == PMX_PAIRS_1D || (ndim == 3 && los >= 0 && los <= 2), PMX_EINVAL,
+    const bool midpoint = mode == PMX_PAIRS_2D_MIDPOINT || mode == PMX_PAIRS_PROJECTED_MIDPOINT;
+    PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED || midpoint, PMX_EINVAL,
+                "bad mode");
+    PMX_REQUIRE(mode == PMX_PAIRS_1D || midpoint || (ndim == 3 && los >= 0 && los <= 2), PMX_EINVAL,
                 "the modes 2D and projected need three dimensions and a line of sight along one of them");
+    PMX_REQUIRE(!midpoint || ndim == 3, PMX_EINVAL, "the midpoint modes need three dimensions");
     PMX_REQUIRE(nr >= 1 && nsub >= 1 && (mode != PMX_PAIRS_1D || nsub == 1), PMX_EINVAL, "bad bin counts");
     PMX_REQUIRE((int64_t)nr * nsub <= PMX_PAIRS_MAX_BINS, PMX_EINVAL, "more than PMX_PAIRS_MAX_BINS bins");
     PMX_REQUIRE(n1 >= 0 && n2 >= 0, PMX_EINVAL, "bad arguments");
@@ -216,7 +143,7 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     a.nr = nr;
     a.nsub = nsub;
     a.nbins = nr * nsub;
-    a.los = mode == PMX_PAIRS_1D ? 0 : los;
+    a.los = mode == PMX_PAIRS_1D || midpoint ? 0 : los;
     a.e2 = e2;
     a.sub = sub;
     a.npairs = (unsigned long long *)npairs;
@@ -227,7 +154,8 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     for (int64_t lo = 0; lo < n2; lo += PAIRS_WINDOW) {
         a.slo = (int32_t)lo;
         a.shi = (int32_t)(lo + PAIRS_WINDOW < n2 ? lo + PAIRS_WINDOW : n2);
-        if (mode == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, has1 || has2, grid, st);
+        if (midpoint) pairs_survey_launch(a, mode, has1 || has2, grid, st);
+        else if (mode == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, has1 || has2, grid, st);
         else if (mode == PMX_PAIRS_PROJECTED) pairs_launch<3, PMX_PAIRS_PROJECTED>(a, has1 || has2, grid, st);
         else with_count<3>(ndim, [&](auto nd) { pairs_launch<decltype(nd)::value, PMX_PAIRS_1D>(a, has1 || has2, grid, st); });
     }

@@ -53,6 +53,9 @@ from .fof import MAX_ROWS, _allsum, _block, _rows, _together, cell_grid, cell_so
 
 MAX_BINS = _abi.PMX_PAIRS_MAX_BINS
 MODES = {'1d': _abi.PMX_PAIRS_1D, '2d': _abi.PMX_PAIRS_2D, 'projected': _abi.PMX_PAIRS_PROJECTED}
+# the modes of local_counts: those of pair_counts, and the two of pmesh_amd.surveypairs whose line of sight is the pair's
+KERNEL_MODES = dict(MODES, **{'2d-midpoint': _abi.PMX_PAIRS_2D_MIDPOINT,
+                              'projected-midpoint': _abi.PMX_PAIRS_PROJECTED_MIDPOINT})
 
 
 class PairCounts(object):
@@ -143,7 +146,7 @@ def _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los):
 def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub):
     """The three arrays of the rows of one rank on the cell grid `grid` (of fof.cell_grid): every row of `pos1` with
     every row of `pos2` (None: with every row of pos1, itself included: the caller subtracts the self pairs).  e2 and
-    sub: device tensors.  Returns (npairs, wnpairs, rsum), flat."""
+    sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat."""
     dev = pos1.device
     nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
     npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
@@ -154,8 +157,8 @@ def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub
         order2, cell_start2, spos2, weight2 = order1, cell_start1, spos1, weight1
     else:
         _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
-    be.pair_counts(MODES[mode], los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2, grid[0],
-                   grid[3], box, e2, sub, npairs, wnpairs, rsum)
+    be.pair_counts(KERNEL_MODES[mode], los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2,
+                   grid[0], grid[3], box, e2, sub, npairs, wnpairs, rsum)
     return npairs, wnpairs, rsum
 
 
@@ -170,35 +173,23 @@ def _weight_sums(comm, w, n):
     return float(s[0]), float(s[1])
 
 
-def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None, Nmu=None,
-                piedges=None, pimax=None, los=2):
-    """The binned pair counts of the rows by the rule of the module docstring: a PairCounts.
+def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None):
+    """What the public counting calls share behind their own reading of the binning: the argument checks of the rows
+    and the weights, the weight sums, the routing on one rank or several, the allreduce and the self pairs.
 
-    pm : ParticleMesh of 1, 2 or 3 dimensions; its BoxSize is the periodic box, its communicator the ranks.
-    pos1 : (n, ndim) float64 or float32, device tensor or numpy array, this rank's rows (any number, none included).
-    edges : the nr + 1 edges of the bins of r (of rp in the projected mode), in box units.
-    pos2 : the rows of a second set for the cross counts, or None: the ordered pairs i != j of pos1.
-    weight1, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
-    mode : '1d', '2d' or 'projected'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or pimax for bins
-        of unit width in [0, pimax]: nbodykit's conventions.  los : the axis of the line of sight.
-
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
-    """
+    kernel : the mode of local_counts.  e2, sub : float64 numpy arrays, what the kernel is given (sub None in 1d).
+    b : the search radius, or None with `error`.  error : what the caller found wrong already, or None.
+    prepare : None, or a function (pos1, pos2) -> (pos1, pos2) applied to the device rows once they are known to be
+        finite, before anything is counted; it raises on every rank together.
+    Returns (npairs, wnpairs, rsum: flat device tensors, identical on every rank; W1, W2, W2sum; box)."""
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
-    if nd > _abi.PMX_MAXDIM:
-        raise NotImplementedError('pair counts on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
     box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
     auto = pos2 is None
-    e, sub, error = _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los)
-    b = None
-    if error is None:
-        b = float(max(e[-1], sub[-1])) if mode == 'projected' else float(e[-1])
-        if not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
-            error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
-                               'side: %r' % b)
+    if error is None and not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+        error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
+                           'side: %r' % b)
     if error is None and auto and weight2 is not None:
         error = ValueError('weight2 needs pos2')
     rows = []
@@ -219,20 +210,20 @@ def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d
         nbad = int(comm.allreduce(nbad))
     if nbad:
         raise ValueError('%d rows of pos1 and pos2 have a coordinate that is not finite' % nbad)
+    if prepare is not None:
+        pos1, pos2 = prepare(pos1, pos2)
     n1 = pos1.shape[0]
     W1, W1sq = _weight_sums(comm, weight1, n1)
     W2, W2sum = (W1, W1sq) if auto else (_weight_sums(comm, weight2, pos2.shape[0])[0], 0.0)
     csize1 = int(comm.allreduce(n1)) if comm.size > 1 else n1
     dev = be.device
-    e2 = torch.from_numpy(e * e).to(dev)
-    if sub is None:
-        subt = None
-    else:
-        subt = torch.from_numpy(sub * sub if mode == '2d' else sub).to(dev)
+    first = e2[0]
+    e2 = torch.from_numpy(numpy.ascontiguousarray(e2, dtype='f8')).to(dev)
+    subt = None if sub is None else torch.from_numpy(numpy.ascontiguousarray(sub, dtype='f8')).to(dev)
     if comm.size == 1:
         most = max(n1, 0 if auto else pos2.shape[0])
         _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-        sums = local_counts(be, mode, los, pos1, weight1, pos2, weight2, cell_grid(most, b, box), box, e2, subt)
+        sums = local_counts(be, kernel, los, pos1, weight1, pos2, weight2, cell_grid(most, b, box), box, e2, subt)
     else:
         # the primaries to their owners; the secondaries to every rank whose block they lie within b of (a hair more
         # than b: a pair at exactly b across a block face must not depend on the rounding of the routing)
@@ -247,17 +238,45 @@ def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d
         w2 = weight1 if auto else weight2
         q2 = ghosts.exchange(w2) if w2 is not None else None
         lo, hi = _block(pm)
-        sums = local_counts(be, mode, los, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
+        sums = local_counts(be, kernel, los, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
         sums = [_allsum(comm, s) for s in sums]
     npairs, wnpairs, rsum = sums
-    if auto and e[0] == 0:
+    if auto and first == 0:
         # the self pairs: r2 == 0 exactly, bin (0, 0)
         npairs[0] -= csize1
         wnpairs[0] -= W2sum
+    return npairs, wnpairs, rsum, W1, W2, W2sum, box
+
+
+def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None, Nmu=None,
+                piedges=None, pimax=None, los=2):
+    """The binned pair counts of the rows by the rule of the module docstring: a PairCounts.
+
+    pm : ParticleMesh of 1, 2 or 3 dimensions; its BoxSize is the periodic box, its communicator the ranks.
+    pos1 : (n, ndim) float64 or float32, device tensor or numpy array, this rank's rows (any number, none included).
+    edges : the nr + 1 edges of the bins of r (of rp in the projected mode), in box units.
+    pos2 : the rows of a second set for the cross counts, or None: the ordered pairs i != j of pos1.
+    weight1, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
+    mode : '1d', '2d' or 'projected'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or pimax for bins
+        of unit width in [0, pimax]: nbodykit's conventions.  los : the axis of the line of sight.
+
+    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
+    ValueError: slots are 32-bit.
+    """
+    nd = len(pm.Nmesh)
+    if nd > _abi.PMX_MAXDIM:
+        raise NotImplementedError('pair counts on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
+    e, sub, error = _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los)
+    b = e2 = given = None
+    if error is None:
+        b = float(max(e[-1], sub[-1])) if mode == 'projected' else float(e[-1])
+        e2 = e * e
+        given = sub * sub if mode == '2d' else sub
+    npairs, wnpairs, rsum, W1, W2, W2sum, box = _count(pm, pos1, pos2, weight1, weight2, mode, los, e2, given, b, error)
     shape = (len(e) - 1,) if sub is None else (len(e) - 1, len(sub) - 1)
     return PairCounts(npairs.reshape(shape), wnpairs.reshape(shape), rsum.reshape(shape), e,
-                      sub if mode == '2d' else None, sub if mode == 'projected' else None, mode, los, auto, W1, W2,
-                      W2sum, box)
+                      sub if mode == '2d' else None, sub if mode == 'projected' else None, mode, los, pos2 is None, W1,
+                      W2, W2sum, box)
 
 
 def pair_correlation(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None, Nmu=None,

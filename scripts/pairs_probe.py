@@ -12,9 +12,14 @@ the host arithmetic).  The host route — a copy of the rows to the host, a peri
 count_neighbors at the 21 cumulative radii (1d only; it has no (r, mu) bins) — is timed on --host-rows rows drawn
 evenly from the input, at the same multiples of ITS mean separation; without scipy the copy over PCIe alone is given
 and the line says so.  One JSON line per input, b and mode.
+With --survey, instead: the uniform rows scaled into the padded interior [b / 2, 1 - b / 2) that
+pmesh_amd.surveypairs asks for, and on the same sorted rows the 40 x 100 auto counts of (s, mu) with the line of sight
+along z (PMX_PAIRS_2D) and with the pair's own, from the box centre to its midpoint (PMX_PAIRS_2D_MIDPOINT,
+csrc/pmx_pairs_survey.hip): the two kernel times by HIP events, the median of --reps, and their ratio.  One JSON line
+per --rows and b.
 
     python scripts/pairs_probe.py [--rows 1000000 10000000] [--mesh 256] [--seps 0.5 2 8] [--reps 3]
-                                  [--host-rows 1000000] [--no-host] [--no-lognormal]
+                                  [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey]
 Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/pairs_probe.py ...` (a run of its
 own).
 """
@@ -139,6 +144,45 @@ def probe(name, pm, pos, args):
         torch.cuda.empty_cache()
 
 
+def survey_probe(pm, pos, args):
+    """--survey: the uniform rows scaled into the padded interior [b / 2, 1 - b / 2) of the box, the 40 x 100 auto
+    counts of (s, mu) on the same sorted rows with the line of sight along z (PMX_PAIRS_2D) and with that of the pair,
+    from the box centre to its midpoint (PMX_PAIRS_2D_MIDPOINT, csrc/pmx_pairs_survey.hip): the two kernel times and
+    their ratio"""
+    be = backend.get()
+    dev = be.device
+    n = pos.shape[0]
+    box = [float(x) for x in pm.BoxSize]
+    sep = (float(numpy.prod(box)) / n) ** (1.0 / 3)
+    for mult in args.seps:
+        b = mult * sep
+        if 2 * b > min(box):
+            continue
+        L = torch.tensor(box, dtype=torch.float64, device=dev)
+        rows = b / 2 + pos * (1 - 2.0 ** -20) * (L - b) / L
+        grid = cell_grid(n, b, box)
+        _, cell_of, cell_start, order, spos, _ = cell_sort(be, rows, grid, box)
+        e, sub = numpy.linspace(0.0, b, 41), numpy.linspace(0.0, 1.0, 101)
+        e2, subt = torch.from_numpy(e * e).to(dev), torch.from_numpy(sub * sub).to(dev)
+        npairs = torch.zeros(4000, dtype=torch.int64, device=dev)
+        wn = torch.zeros(4000, dtype=torch.float64, device=dev)
+        rs = torch.zeros(4000, dtype=torch.float64, device=dev)
+
+        def zero():
+            npairs.zero_(), wn.zero_(), rs.zero_()
+        line = {'input': 'uniform, padded interior', 'rows': n, 'b_in_mean_separations': mult, 'b': b, 'bins': 4000,
+                'cells': int(numpy.prod(grid[0]))}
+        for key, code in (('axis', _abi.PMX_PAIRS_2D), ('midpoint', _abi.PMX_PAIRS_2D_MIDPOINT)):
+            t = timed(lambda: be.pair_counts(code, 2, spos, order, cell_of, None, spos, order, cell_start, None,
+                                             grid[0], grid[3], box, e2, subt, npairs, wn, rs), args.reps, prep=zero)
+            line['%s_kernel_ms' % key] = round(t, 3)
+            line['%s_pairs_counted' % key] = int(npairs.sum()) - n
+        line['midpoint_over_axis'] = round(line['midpoint_kernel_ms'] / line['axis_kernel_ms'], 3)
+        print(json.dumps(line), flush=True)
+        del rows, cell_of, cell_start, order, spos
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, nargs='+', default=[10 ** 6, 10 ** 7])
@@ -148,6 +192,8 @@ def main():
     ap.add_argument('--host-rows', type=int, default=10 ** 6)
     ap.add_argument('--no-host', action='store_true')
     ap.add_argument('--no-lognormal', action='store_true')
+    ap.add_argument('--survey', action='store_true',
+                    help='only the 40 x 100 counts of (s, mu) with the axis and the midpoint line of sight, on uniform rows')
     args = ap.parse_args()
     be = backend.get()
     dev = be.device
@@ -155,6 +201,11 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1)
         pm = ParticleMesh([args.mesh] * 3, BoxSize=1.0, dtype='f8')
         pos = torch.rand((rows, 3), generator=gen, device=dev, dtype=torch.float64)
+        if args.survey:
+            survey_probe(pm, pos, args)
+            del pos
+            torch.cuda.empty_cache()
+            continue
         probe('uniform', pm, pos, args)
         del pos
         torch.cuda.empty_cache()
