@@ -1034,13 +1034,37 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *             caller with a survey keeps every row in [b / 2, L_d - b / 2), b the search radius (edges[nr]; in the
  *             projected mode hypot(edges[nr], piedges[nsub]): the walk over the cells must cover the bounding sphere of
  *             the cylinder), so that no two rows are closer than b through the boundary and no counted pair is a
- *             wrapped one. */
+ *             wrapped one.
+ *
+ * The modes with one histogram per primary row (radial profiles, enclosed and spherical-overdensity masses, counts in
+ * spheres and Sigma(R) about centres; pmesh_amd.profiles).  PMX_PAIRS_1D_ROWS is PMX_PAIRS_1D and
+ * PMX_PAIRS_PROJECTED_ROWS is PMX_PAIRS_PROJECTED with the sums of every primary kept apart:
+ *   shared    rows, wrapping, minimum image, r2, q, the squared edges, the r-bin, the pi-bin and the pimax cut are
+ *             exactly those of PMX_PAIRS_1D and PMX_PAIRS_PROJECTED: all arithmetic in double, every operation rounded
+ *             once, no contraction, no square root choosing a bin.  PMX_PAIRS_PROJECTED_ROWS needs ndim == 3 and los in
+ *             {0, 1, 2}; PMX_PAIRS_1D_ROWS takes ndim 1 to 3 and nsub == 1.
+ *   bin       the bin of a pair (primary row i, secondary slot s) is (i * nr + rbin) * nsub + subbin, i the ROW of the
+ *             primary (order1[slot]), not its slot.
+ *   arrays    npairs, wnpairs and rsum are DEVICE arrays of n1 * nr * nsub entries in the caller's row order.  They are
+ *             added to, as in the base modes: the caller zeroes them, and a second call with other secondaries keeps
+ *             adding.
+ *   limit     nr * nsub <= PMX_PAIRS_ROWS_MAX_BINS, else PMX_EINVAL.
+ *   exact     npairs is exact and depends on no decomposition or launch.  The order of the double sums is unspecified,
+ *             as in the base modes.  With both weights NULL, wnpairs += (double)(the count).
+ *   identity  there is none: a centre that coincides with a source has r2 == 0 and is counted in bin 0 when
+ *             edges[0] == 0 and nowhere otherwise.
+ *   windows   above 2^23 secondaries the entry still launches once per window of 2^23 slots.  One wave per primary
+ *             slot keeps the row's histogram in LDS (pmx_pairs_rows.hip) and owns the row's bins for the launch: it adds
+ *             them with plain loads and stores, no global atomic. */
 #define PMX_PAIRS_MAX_BINS 4096          /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
 #define PMX_PAIRS_PROJECTED 2            /* bins of (rp, pi) */
 #define PMX_PAIRS_2D_MIDPOINT 3          /* bins of (s, mu), the line of sight from the box centre to the pair's midpoint */
 #define PMX_PAIRS_PROJECTED_MIDPOINT 4   /* bins of (rp, pi), the same line of sight */
+#define PMX_PAIRS_1D_ROWS 5              /* bins of r, one histogram per primary row */
+#define PMX_PAIRS_PROJECTED_ROWS 6       /* bins of (rp, pi) about the axis los, one histogram per primary row */
+#define PMX_PAIRS_ROWS_MAX_BINS 256      /* nr * nsub of one call in the two row modes */
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
@@ -1053,7 +1077,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * With both NULL no weight is read and wnpairs[b] += (double)(the count).
  * e2: DEVICE double, nr + 1 entries.  sub: DEVICE double, nsub + 1 entries, m2 (2D, 2D_MIDPOINT), piedges (projected)
  * or piedges^2 (PROJECTED_MIDPOINT); NULL and nsub = 1 in the mode 1D.  los is ignored in the mode 1D and in the two
- * midpoint modes, whose kernels (pmx_pairs_survey.hip) are launched from this entry like the others.
+ * midpoint modes, whose kernels (pmx_pairs_survey.hip) are launched from this entry like the others, as are those of
+ * the two row modes (pmx_pairs_rows.hip), whose three arrays have n1 * nr * nsub entries.
  * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
  * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
  * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)

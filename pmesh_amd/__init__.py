@@ -19,6 +19,7 @@
     from pmesh_amd.threept import threept_multipoles, threept_correlation   # three-point multipoles zeta_l(r1, r2) of particles
     from pmesh_amd.shortrange import short_range_force              # the short-range pair force of a TreePM / P3M split
     from pmesh_amd.knn import knn, knn_density, knn_cdf             # k-nearest-neighbour distances, densities and the kNN-CDF
+    from pmesh_amd.profiles import radial_profiles, so_masses      # per-centre radial profiles, Sigma(R) and spherical-overdensity masses
     from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
     from pmesh_amd.lpt import lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp   # and their gradients
 

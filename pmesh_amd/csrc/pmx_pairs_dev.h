@@ -142,4 +142,9 @@ __device__ __forceinline__ void pair_hist_flush(const PArgs &a, const uint32_t *
 // PMX_PAIRS_PROJECTED_MIDPOINT (pmx_pair_counts has checked the arguments and filled `a`)
 void pairs_survey_launch(const PArgs &a, int mode, bool weighted, unsigned grid, hipStream_t st);
 
+// pmx_pairs_rows.hip: the launch of one window of the secondaries in the modes PMX_PAIRS_1D_ROWS and
+// PMX_PAIRS_PROJECTED_ROWS, one wave per slot of the primaries (pmx_pair_counts has checked the arguments and filled
+// `a`; ndim: the columns of the rows, which `a` does not hold)
+void pairs_rows_launch(const PArgs &a, int ndim, int mode, bool weighted, hipStream_t st);
+
 }  // namespace pmx
