@@ -1055,8 +1055,41 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *             edges[0] == 0 and nowhere otherwise.
  *   windows   above 2^23 secondaries the entry still launches once per window of 2^23 slots.  One wave per primary
  *             slot keeps the row's histogram in LDS (pmx_pairs_rows.hip) and owns the row's bins for the launch: it adds
- *             them with plain loads and stores, no global atomic. */
-#define PMX_PAIRS_MAX_BINS 4096          /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
+ *             them with plain loads and stores, no global atomic.
+ *
+ * The modes with pairwise velocity statistics (the mean pairwise velocity v12(r), the pairwise dispersions, the
+ * line-of-sight pairwise velocity in bins of (rp, pi), the pairwise estimator of Ferreira et al. 1999 for one
+ * line-of-sight scalar per row; pmesh_amd.pairvel).  PMX_PAIRS_1D_VELOCITY shares everything below with PMX_PAIRS_1D,
+ * PMX_PAIRS_PROJECTED_VELOCITY with PMX_PAIRS_PROJECTED, PMX_PAIRS_1D_LOS with PMX_PAIRS_1D:
+ *   shared    rows, wrapping, the minimum image dx_d (primary minus secondary), r2, q, the squared edges, the r-bin, the
+ *             pi-bin and the pimax cut; all arithmetic in double; every operation rounded once, no contraction; no
+ *             square root chooses a bin.  npairs equals npairs of the corresponding base mode on the same arguments, to
+ *             the last count.
+ *   columns   weight1 and weight2 are both required.  PMX_PAIRS_1D_VELOCITY and PMX_PAIRS_PROJECTED_VELOCITY: pmx_vecs
+ *             of 1 + ndim columns, (w, v_0 .. v_{ndim-1}).  PMX_PAIRS_1D_LOS: 2 columns, (w, s).  Float or double, in
+ *             ROW order, read through order1 / order2 like the weights of the base modes.  A wrong ncol is PMX_EINVAL.
+ *   outputs   npairs and wnpairs have nr * nsub entries, as in the base modes.  rsum has 4 * nr * nsub entries:
+ *             rsum[m * nbins + b]; m = 0: sum w sqrt(q), as in the base modes; m = 1, 2, 3: the sums S1, S2, S3 below.
+ *             All are added to, never overwritten.  The order of the double sums is unspecified; npairs is exact.
+ *   per counted pair, with w = w1_i * w2_j:
+ *   PMX_PAIRS_1D_VELOCITY, ndim 1 to 3, nsub == 1: dv_d = v_i,d - v_j,d; h = dx_0 dv_0 + dx_1 dv_1 + dx_2 dv_2 and
+ *             dv2 = dv_0^2 + dv_1^2 + dv_2^2, each summed in that order over d < ndim; r = sqrt(r2); u = h / r where
+ *             r2 > 0, else 0.  S1 += (w u), S2 += (w u) u, S3 += w dv2.  u is the radial pairwise velocity: negative
+ *             means the pair approaches.
+ *   PMX_PAIRS_PROJECTED_VELOCITY, ndim 3, los in {0, 1, 2}, sub = piedges: u = dx_los < 0 ? -dv_los : dv_los; S1, S2,
+ *             S3 as above, with dv2 over all three axes.  The m = 0 sum adds w sqrt(rp2), as PMX_PAIRS_PROJECTED does.
+ *   PMX_PAIRS_1D_LOS, ndim 3, nsub == 1; los is ignored.  The observer is at o_d = 0.5 * L_d, as in the midpoint
+ *             modes, and the caller keeps rows in [b / 2, L_d - b / 2) as for them.  a_d = w_i,d - o_d and b_d = w_j,d -
+ *             o_d, w_i and w_j the wrapped rows; a2, b2, pa = dx.a and pb = dx.b are each summed over d = 0, 1, 2 in
+ *             order; ta = a2 > 0 ? pa / sqrt(a2) : 0, tb likewise; c = r2 > 0 ? 0.5 * ((ta + tb) / r) : 0; ds = s_i -
+ *             s_j.  S1 += (w c) ds, S2 += (w c) c, S3 += (w ds) ds.  (Ferreira et al. 1999: v12 = S1 / S2.)
+ *   self      a self pair (one set passed as both) has r2 == 0, dv == 0 and ds == 0: it adds nothing to S1 .. S3; the
+ *             caller subtracts it from npairs[0] and wnpairs[0] as in the base modes.  Each statistic is even under
+ *             exchanging the two rows, so one set passed as both counts every unordered pair twice, in the numerator
+ *             and in the denominator alike.
+ *   limit     nr * nsub <= PMX_PAIRS_VELOCITY_MAX_BINS, else PMX_EINVAL: the histogram of a workgroup holds a 32-bit
+ *             count and five doubles per bin in LDS (pmx_pairs_vel.hip). */
+#define PMX_PAIRS_MAX_BINS 4096         /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
 #define PMX_PAIRS_PROJECTED 2            /* bins of (rp, pi) */
@@ -1065,6 +1098,10 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
 #define PMX_PAIRS_1D_ROWS 5              /* bins of r, one histogram per primary row */
 #define PMX_PAIRS_PROJECTED_ROWS 6       /* bins of (rp, pi) about the axis los, one histogram per primary row */
 #define PMX_PAIRS_ROWS_MAX_BINS 256      /* nr * nsub of one call in the two row modes */
+#define PMX_PAIRS_1D_VELOCITY 7          /* bins of r; radial pairwise velocity */
+#define PMX_PAIRS_PROJECTED_VELOCITY 8   /* bins of (rp, pi) about the axis los; line-of-sight pairwise velocity */
+#define PMX_PAIRS_1D_LOS 9               /* bins of r; one line-of-sight scalar per row, observer at the box centre */
+#define PMX_PAIRS_VELOCITY_MAX_BINS 1024 /* nr * nsub of one call in these three modes */
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
@@ -1078,7 +1115,9 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * e2: DEVICE double, nr + 1 entries.  sub: DEVICE double, nsub + 1 entries, m2 (2D, 2D_MIDPOINT), piedges (projected)
  * or piedges^2 (PROJECTED_MIDPOINT); NULL and nsub = 1 in the mode 1D.  los is ignored in the mode 1D and in the two
  * midpoint modes, whose kernels (pmx_pairs_survey.hip) are launched from this entry like the others, as are those of
- * the two row modes (pmx_pairs_rows.hip), whose three arrays have n1 * nr * nsub entries.
+ * the two row modes (pmx_pairs_rows.hip), whose three arrays have n1 * nr * nsub entries, and those of the three
+ * velocity modes (pmx_pairs_vel.hip), whose weight1 / weight2 have 1 + ndim or 2 columns and whose rsum has
+ * 4 * nr * nsub entries.
  * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
  * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
  * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)

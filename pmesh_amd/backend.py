@@ -495,9 +495,18 @@ class HipBackend(object):
         them) with the secondaries (spos2, order2, cell_start2, of the same grid) added into the zeroed tensors `npairs`
         (int64), `wnpairs` and `rsum` (float64) of nr * nsub entries.  mode: PMX_PAIRS_*; e2: the nr + 1 squared edges
         on the device; sub: the nsub + 1 squared mu edges or pi edges on the device, None in the mode 1D; weight1 /
-        weight2: (n,) or (n, 1) float tensors in row order, or None (pmx_pair_counts)"""
+        weight2: (n,) or (n, 1) float tensors in row order, or None (pmx_pair_counts).  In the three velocity modes
+        (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY, PMX_PAIRS_1D_LOS) weight1 / weight2 are the (n, 1 + ndim)
+        or (n, 2) blocks of columns of the two sets and `rsum` has 4 * nr * nsub entries"""
         if spos1.shape[0] == 0 or spos2.shape[0] == 0:
             return
+        if int(mode) in (_abi.PMX_PAIRS_1D_VELOCITY, _abi.PMX_PAIRS_PROJECTED_VELOCITY, _abi.PMX_PAIRS_1D_LOS):
+            nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
+            if rsum.numel() < 4 * nbins or min(npairs.numel(), wnpairs.numel()) < nbins:
+                raise ValueError('the velocity modes need rsum of 4 * nr * nsub entries')
+            for w, s in ((weight1, spos1), (weight2, spos2)):
+                if w is None or w.dim() != 2 or w.shape[0] != s.shape[0]:
+                    raise ValueError('the velocity modes need weight1 and weight2 as (n, ncol) blocks of the rows')
         wv1, wv2 = _arrays.vec(weight1), _arrays.vec(weight2)
         self.call('pair_counts', spos1.shape[1], int(mode), int(los), spos1.shape[0], spos1.data_ptr(),
                   order1.data_ptr(), cell_of1.data_ptr(), C.byref(wv1) if weight1 is not None else None,

@@ -20,7 +20,9 @@
 // another: the only barriers are the two around the walk.  The histogram, the walk and the arguments are those of
 // pmx_pairs_dev.h; the modes whose line of sight is the pair's own (PMX_PAIRS_2D_MIDPOINT, PMX_PAIRS_PROJECTED_MIDPOINT)
 // have their kernels in pmx_pairs_survey.hip and are launched from pmx_pair_counts below, and so are the modes with one
-// histogram per primary row (PMX_PAIRS_1D_ROWS, PMX_PAIRS_PROJECTED_ROWS), whose kernels are in pmx_pairs_rows.hip.
+// histogram per primary row (PMX_PAIRS_1D_ROWS, PMX_PAIRS_PROJECTED_ROWS), whose kernels are in pmx_pairs_rows.hip, and
+// the modes with pairwise velocity sums (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY, PMX_PAIRS_1D_LOS), whose
+// kernels are in pmx_pairs_vel.hip.
 #include "pmx_pairs_dev.h"
 
 namespace pmx {
@@ -116,16 +118,21 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     if (rc != PMX_OK) return rc;
     const bool midpoint = mode == PMX_PAIRS_2D_MIDPOINT || mode == PMX_PAIRS_PROJECTED_MIDPOINT;
     const bool rows = mode == PMX_PAIRS_1D_ROWS || mode == PMX_PAIRS_PROJECTED_ROWS;
-    const bool one = mode == PMX_PAIRS_1D || mode == PMX_PAIRS_1D_ROWS;
-    PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED || midpoint || rows,
+    const bool vel = mode == PMX_PAIRS_1D_VELOCITY || mode == PMX_PAIRS_PROJECTED_VELOCITY || mode == PMX_PAIRS_1D_LOS;
+    const bool one = mode == PMX_PAIRS_1D || mode == PMX_PAIRS_1D_ROWS || mode == PMX_PAIRS_1D_VELOCITY ||
+                     mode == PMX_PAIRS_1D_LOS;
+    PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED || midpoint || rows || vel,
                 PMX_EINVAL, "bad mode");
     PMX_REQUIRE(one || midpoint || (ndim == 3 && los >= 0 && los <= 2), PMX_EINVAL,
                 "the modes 2D and projected need three dimensions and a line of sight along one of them");
     PMX_REQUIRE(!midpoint || ndim == 3, PMX_EINVAL, "the midpoint modes need three dimensions");
+    PMX_REQUIRE(mode != PMX_PAIRS_1D_LOS || ndim == 3, PMX_EINVAL, "the mode 1D_LOS needs three dimensions");
     PMX_REQUIRE(nr >= 1 && nsub >= 1 && (!one || nsub == 1), PMX_EINVAL, "bad bin counts");
     PMX_REQUIRE((int64_t)nr * nsub <= PMX_PAIRS_MAX_BINS, PMX_EINVAL, "more than PMX_PAIRS_MAX_BINS bins");
     PMX_REQUIRE(!rows || (int64_t)nr * nsub <= PMX_PAIRS_ROWS_MAX_BINS, PMX_EINVAL,
                 "more than PMX_PAIRS_ROWS_MAX_BINS bins per row");
+    PMX_REQUIRE(!vel || (int64_t)nr * nsub <= PMX_PAIRS_VELOCITY_MAX_BINS, PMX_EINVAL,
+                "more than PMX_PAIRS_VELOCITY_MAX_BINS bins");
     PMX_REQUIRE(n1 >= 0 && n2 >= 0, PMX_EINVAL, "bad arguments");
     PMX_REQUIRE(n1 <= PMX_FOF_MAX_ROWS && n2 <= PMX_FOF_MAX_ROWS, PMX_EUNSUPPORTED,
                 "more than 2^31 - 1 rows: slots are 32-bit");
@@ -135,6 +142,10 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     const bool has1 = weight1 && weight1->data, has2 = weight2 && weight2->data;
     PMX_REQUIRE(!has1 || vec_ok(weight1), PMX_EINVAL, "weight1 must be float or double");
     PMX_REQUIRE(!has2 || vec_ok(weight2), PMX_EINVAL, "weight2 must be float or double");
+    // the velocity modes: both sets bring (w, v_0 .. v_{ndim-1}), or (w, s) in the mode 1D_LOS
+    const int32_t vcol = mode == PMX_PAIRS_1D_LOS ? 2 : 1 + ndim;
+    PMX_REQUIRE(!vel || (has1 && has2 && weight1->ncol == vcol && weight2->ncol == vcol), PMX_EINVAL,
+                "the velocity modes need weight1 and weight2 of 1 + ndim columns (1D_LOS: 2)");
     a.n1 = n1;
     a.n2 = n2;
     a.spos1 = spos1;
@@ -161,6 +172,7 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
         a.shi = (int32_t)(lo + PAIRS_WINDOW < n2 ? lo + PAIRS_WINDOW : n2);
         if (midpoint) pairs_survey_launch(a, mode, has1 || has2, grid, st);
         else if (rows) pairs_rows_launch(a, ndim, mode, has1 || has2, st);
+        else if (vel) pairs_vel_launch(a, ndim, mode, grid, st);
         else if (mode == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, has1 || has2, grid, st);
         else if (mode == PMX_PAIRS_PROJECTED) pairs_launch<3, PMX_PAIRS_PROJECTED>(a, has1 || has2, grid, st);
         else with_count<3>(ndim, [&](auto nd) { pairs_launch<decltype(nd)::value, PMX_PAIRS_1D>(a, has1 || has2, grid, st); });

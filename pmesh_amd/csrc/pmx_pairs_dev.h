@@ -147,4 +147,9 @@ void pairs_survey_launch(const PArgs &a, int mode, bool weighted, unsigned grid,
 // `a`; ndim: the columns of the rows, which `a` does not hold)
 void pairs_rows_launch(const PArgs &a, int ndim, int mode, bool weighted, hipStream_t st);
 
+// pmx_pairs_vel.hip: the launch of one window of the secondaries in the modes PMX_PAIRS_1D_VELOCITY,
+// PMX_PAIRS_PROJECTED_VELOCITY and PMX_PAIRS_1D_LOS (pmx_pair_counts has checked the arguments and filled `a`: w1 and
+// w2 hold the 1 + ndim or 2 columns of the two sets, rsum has 4 * nbins entries)
+void pairs_vel_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
+
 }  // namespace pmx

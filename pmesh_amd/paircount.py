@@ -56,6 +56,11 @@ MODES = {'1d': _abi.PMX_PAIRS_1D, '2d': _abi.PMX_PAIRS_2D, 'projected': _abi.PMX
 # the modes of local_counts: those of pair_counts, and the two of pmesh_amd.surveypairs whose line of sight is the pair's
 KERNEL_MODES = dict(MODES, **{'2d-midpoint': _abi.PMX_PAIRS_2D_MIDPOINT,
                               'projected-midpoint': _abi.PMX_PAIRS_PROJECTED_MIDPOINT})
+# and the three of pmesh_amd.pairvel, whose sets bring a block of columns (w, v_0 .. v_{ndim-1}) or (w, s) in place of the
+# one-column weight and whose rsum holds four sums per bin
+VELOCITY_MODES = {'1d-velocity': _abi.PMX_PAIRS_1D_VELOCITY, 'projected-velocity': _abi.PMX_PAIRS_PROJECTED_VELOCITY,
+                  '1d-los': _abi.PMX_PAIRS_1D_LOS}
+KERNEL_MODES.update(VELOCITY_MODES)
 
 
 class PairCounts(object):
@@ -146,12 +151,14 @@ def _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los):
 def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub):
     """The three arrays of the rows of one rank on the cell grid `grid` (of fof.cell_grid): every row of `pos1` with
     every row of `pos2` (None: with every row of pos1, itself included: the caller subtracts the self pairs).  e2 and
-    sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat."""
+    sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat.  In the modes of
+    VELOCITY_MODES weight1 and weight2 are the (n, ncol) blocks of columns of the two sets and rsum has 4 * nbins
+    entries, rsum[m * nbins + b]."""
     dev = pos1.device
     nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
     npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
     wnpairs = torch.zeros(nbins, dtype=torch.float64, device=dev)
-    rsum = torch.zeros(nbins, dtype=torch.float64, device=dev)
+    rsum = torch.zeros(4 * nbins if mode in VELOCITY_MODES else nbins, dtype=torch.float64, device=dev)
     _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
     if pos2 is None:
         order2, cell_start2, spos2, weight2 = order1, cell_start1, spos1, weight1
@@ -173,7 +180,15 @@ def _weight_sums(comm, w, n):
     return float(s[0]), float(s[1])
 
 
-def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None):
+def _block_of(weight, cols):
+    """the contiguous (n, 1 + ncol) block (w, columns) of one set: w = 1 without a weight; float32 where the columns
+    and the weight are, else float64"""
+    dtype = cols.dtype if weight is None or weight.dtype == cols.dtype else torch.float64
+    w = torch.ones(cols.shape[0], dtype=dtype, device=cols.device) if weight is None else weight.to(dtype)
+    return torch.cat([w.reshape(-1, 1), cols.to(dtype)], dim=1).contiguous()
+
+
+def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None, columns=None):
     """What the public counting calls share behind their own reading of the binning: the argument checks of the rows
     and the weights, the weight sums, the routing on one rank or several, the allreduce and the self pairs.
 
@@ -181,6 +196,10 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
     b : the search radius, or None with `error`.  error : what the caller found wrong already, or None.
     prepare : None, or a function (pos1, pos2) -> (pos1, pos2) applied to the device rows once they are known to be
         finite, before anything is counted; it raises on every rank together.
+    columns : None, or (name, x1, x2, ncol) for the modes of VELOCITY_MODES: the further columns of the rows of the two
+        sets, (n, ncol) float rows called `name`1 and `name`2 in messages; x2 is given exactly when pos2 is.  They must
+        be finite.  Each set then travels as one contiguous (n, 1 + ncol) block (w, columns), w = 1 without a weight,
+        float32 where all of its parts are, through the exchanges of the weights, and rsum has 4 * nbins entries.
     Returns (npairs, wnpairs, rsum: flat device tensors, identical on every rank; W1, W2, W2sum; box)."""
     be = backend.get()
     comm = pm.comm
@@ -192,15 +211,22 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
                            'side: %r' % b)
     if error is None and auto and weight2 is not None:
         error = ValueError('weight2 needs pos2')
+    wanted = [('pos1', pos1, nd, None), ('pos2', pos2, nd, None), ('weight1', weight1, 1, 0), ('weight2', weight2, 1, 1)]
+    if columns is not None:
+        name, x1, x2, ncol = columns
+        if error is None and x1 is None:
+            error = ValueError('%s1 is needed' % name)
+        if error is None and (x2 is None) != auto:
+            error = ValueError('%s2 needs pos2' % name if auto else 'pos2 needs %s2' % name)
+        wanted += [(name + '1', x1, ncol, 0), (name + '2', x2, ncol, 1)]
     rows = []
-    for what, x, ncol, of in (('pos1', pos1, nd, None), ('pos2', pos2, nd, None), ('weight1', weight1, 1, 0),
-                              ('weight2', weight2, 1, 1)):
+    for what, x, ncol, of in wanted:
         t = None
         if x is not None and error is None:
             t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
         rows.append(t)
     _together(comm, error)
-    pos1, pos2, weight1, weight2 = rows
+    pos1, pos2, weight1, weight2 = rows[:4]
     if weight1 is not None:
         weight1 = weight1.reshape(-1)
     if weight2 is not None:
@@ -210,12 +236,22 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         nbad = int(comm.allreduce(nbad))
     if nbad:
         raise ValueError('%d rows of pos1 and pos2 have a coordinate that is not finite' % nbad)
+    if columns is not None:
+        nbad = sum(int((~torch.isfinite(x)).any(dim=1).sum()) for x in rows[4:] if x is not None)
+        if comm.size > 1:
+            nbad = int(comm.allreduce(nbad))
+        if nbad:
+            raise ValueError('%d rows of %s1 and %s2 have an entry that is not finite' % (nbad, columns[0], columns[0]))
     if prepare is not None:
         pos1, pos2 = prepare(pos1, pos2)
     n1 = pos1.shape[0]
     W1, W1sq = _weight_sums(comm, weight1, n1)
     W2, W2sum = (W1, W1sq) if auto else (_weight_sums(comm, weight2, pos2.shape[0])[0], 0.0)
     csize1 = int(comm.allreduce(n1)) if comm.size > 1 else n1
+    if columns is not None:
+        # from here on the weight of a set is its block of columns
+        weight1 = _block_of(weight1, rows[4])
+        weight2 = None if auto else _block_of(weight2, rows[5])
     dev = be.device
     first = e2[0]
     e2 = torch.from_numpy(numpy.ascontiguousarray(e2, dtype='f8')).to(dev)

@@ -134,31 +134,13 @@ def _observer(observer, box):
     return o, None
 
 
-def survey_pair_counts(pm, pos1, edges, observer=None, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None,
-                       Nmu=None, piedges=None, pimax=None, thetaedges=None):
-    """The binned pair counts of the rows by the rule of the module docstring: a SurveyPairCounts.
+def _preparation(comm, box, b, observer, obs, mode='1d', R=None):
+    """The `prepare` step of paircount._count for rows about an observer: the shift of the rows that puts `obs` (the
+    observer as an array; `observer`: what the caller passed, None for the box centre) at the box centre, in the angular
+    mode the rows on the sphere of radius R, and the check that every row lies in [b / 2, L_d - b / 2); it raises on
+    every rank together."""
 
-    pm : ParticleMesh of three dimensions; its BoxSize is the volume that holds the survey, its communicator the ranks.
-    pos1 : (n, 3) float64 or float32, device tensor or numpy array, this rank's rows (any number, none included).
-    edges : the nr + 1 edges of the bins of s (of rp in the projected mode), in box units; ignored in the angular mode.
-    observer : three numbers in box coordinates, or None: the centre of the box.
-    pos2 : the rows of a second set for the cross counts, or None: the ordered pairs i != j of pos1.
-    weight1, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
-    mode : '1d', '2d', 'projected' or 'angular'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or
-        pimax for bins of unit width in [0, pimax]; thetaedges in degrees: nbodykit's conventions.
-
-    Argument errors, a row outside ``[b / 2, L_d - b / 2)`` and a row at the observer (angular) raise on every rank
-    together.
-    """
-    nd = len(pm.Nmesh)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
-    e, sub, e2, given, b, R, error = _survey_binning(nd, edges, mode, muedges, Nmu, piedges, pimax, thetaedges, box)
-    obs = None
-    if error is None:
-        obs, error = _observer(observer, box)
-    comm = pm.comm
-
-    def prepare(p1, p2):
+    def _prepare(p1, p2):
         L = torch.tensor(box, dtype=torch.float64, device=p1.device)
         centre = L / 2
         shift = None
@@ -195,6 +177,32 @@ def survey_pair_counts(pm, pos1, edges, observer=None, pos2=None, weight1=None, 
                                  'BoxSize of more than %r along axis %d holds them'
                                  % (b / 2, box[d] - b / 2, d, float(lo[d]), float(hi[d]), float(need), d))
         return out[0], out[1]
+    return _prepare
+
+
+def survey_pair_counts(pm, pos1, edges, observer=None, pos2=None, weight1=None, weight2=None, mode='1d', muedges=None,
+                       Nmu=None, piedges=None, pimax=None, thetaedges=None):
+    """The binned pair counts of the rows by the rule of the module docstring: a SurveyPairCounts.
+
+    pm : ParticleMesh of three dimensions; its BoxSize is the volume that holds the survey, its communicator the ranks.
+    pos1 : (n, 3) float64 or float32, device tensor or numpy array, this rank's rows (any number, none included).
+    edges : the nr + 1 edges of the bins of s (of rp in the projected mode), in box units; ignored in the angular mode.
+    observer : three numbers in box coordinates, or None: the centre of the box.
+    pos2 : the rows of a second set for the cross counts, or None: the ordered pairs i != j of pos1.
+    weight1, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
+    mode : '1d', '2d', 'projected' or 'angular'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or
+        pimax for bins of unit width in [0, pimax]; thetaedges in degrees: nbodykit's conventions.
+
+    Argument errors, a row outside ``[b / 2, L_d - b / 2)`` and a row at the observer (angular) raise on every rank
+    together.
+    """
+    nd = len(pm.Nmesh)
+    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    e, sub, e2, given, b, R, error = _survey_binning(nd, edges, mode, muedges, Nmu, piedges, pimax, thetaedges, box)
+    obs = None
+    if error is None:
+        obs, error = _observer(observer, box)
+    prepare = _preparation(pm.comm, box, b, observer, obs, mode, R)
 
     npairs, wnpairs, rsum, W1, W2, W2sum, box = _count(pm, pos1, pos2, weight1, weight2, KERNELS.get(mode), 2, e2,
                                                        given, b, error, prepare)

@@ -17,9 +17,14 @@ pmesh_amd.surveypairs asks for, and on the same sorted rows the 40 x 100 auto co
 along z (PMX_PAIRS_2D) and with the pair's own, from the box centre to its midpoint (PMX_PAIRS_2D_MIDPOINT,
 csrc/pmx_pairs_survey.hip): the two kernel times by HIP events, the median of --reps, and their ratio.  One JSON line
 per --rows and b.
+With --velocity, instead: the uniform rows with normal velocities and uniform weights, and on the same sorted rows the
+auto counts with 40 bins of r and with 40 x 25 bins of (rp, pi) by the weighted pair-count kernel (PMX_PAIRS_1D,
+PMX_PAIRS_PROJECTED) and by the velocity kernels of csrc/pmx_pairs_vel.hip (PMX_PAIRS_1D_VELOCITY,
+PMX_PAIRS_PROJECTED_VELOCITY): the kernel times by HIP events, the median of --reps, and their ratios.  One JSON line
+per --rows and b.
 
     python scripts/pairs_probe.py [--rows 1000000 10000000] [--mesh 256] [--seps 0.5 2 8] [--reps 3]
-                                  [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey]
+                                  [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey] [--velocity]
 Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/pairs_probe.py ...` (a run of its
 own).
 """
@@ -183,6 +188,51 @@ def survey_probe(pm, pos, args):
         torch.cuda.empty_cache()
 
 
+def velocity_probe(pm, pos, args):
+    """--velocity: the uniform rows with normal velocities and uniform weights, auto, on the same sorted rows: the
+    weighted pair_counts kernel (PMX_PAIRS_1D with 40 bins of r, PMX_PAIRS_PROJECTED with 40 x 25 bins of (rp, pi)) and
+    the velocity kernels of csrc/pmx_pairs_vel.hip on the same edges (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY):
+    the kernel times and their ratios"""
+    be = backend.get()
+    dev = be.device
+    n = pos.shape[0]
+    box = [float(x) for x in pm.BoxSize]
+    sep = (float(numpy.prod(box)) / n) ** (1.0 / 3)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    blk = torch.cat([0.5 + torch.rand((n, 1), generator=gen, device=dev, dtype=torch.float64),
+                     torch.randn((n, 3), generator=gen, device=dev, dtype=torch.float64)], dim=1).contiguous()
+    w = blk[:, 0].contiguous()
+    for mult in args.seps:
+        b = mult * sep
+        if 2 * b > min(box):
+            continue
+        grid = cell_grid(n, b, box)
+        _, cell_of, cell_start, order, spos, _ = cell_sort(be, pos, grid, box)
+        line = {'input': 'uniform', 'rows': n, 'b_in_mean_separations': mult, 'b': b, 'cells': int(numpy.prod(grid[0]))}
+        e2 = torch.from_numpy(numpy.linspace(0.0, b, 41) ** 2).to(dev)
+        pie = torch.from_numpy(numpy.linspace(0.0, b, 26)).to(dev)
+        for key, sub, base, code in (('1d', None, _abi.PMX_PAIRS_1D, _abi.PMX_PAIRS_1D_VELOCITY),
+                                     ('projected', pie, _abi.PMX_PAIRS_PROJECTED, _abi.PMX_PAIRS_PROJECTED_VELOCITY)):
+            nbins = 40 * (1 if sub is None else 25)
+            npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
+            wn = torch.zeros(nbins, dtype=torch.float64, device=dev)
+            rs = torch.zeros(4 * nbins, dtype=torch.float64, device=dev)
+
+            def zero():
+                npairs.zero_(), wn.zero_(), rs.zero_()
+            for which, mode, weight in (('weighted', base, w), ('velocity', code, blk)):
+                t = timed(lambda: be.pair_counts(mode, 2, spos, order, cell_of, weight, spos, order, cell_start, weight,
+                                                 grid[0], grid[3], box, e2, sub, npairs, wn, rs), args.reps, prep=zero)
+                line['%s_%s_kernel_ms' % (key, which)] = round(t, 3)
+                line['%s_%s_pairs_counted' % (key, which)] = int(npairs.sum()) - n
+            line['%s_bins' % key] = nbins
+            line['%s_velocity_over_weighted' % key] = round(line['%s_velocity_kernel_ms' % key] /
+                                                            line['%s_weighted_kernel_ms' % key], 3)
+        print(json.dumps(line), flush=True)
+        del cell_of, cell_start, order, spos
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, nargs='+', default=[10 ** 6, 10 ** 7])
@@ -194,6 +244,8 @@ def main():
     ap.add_argument('--no-lognormal', action='store_true')
     ap.add_argument('--survey', action='store_true',
                     help='only the 40 x 100 counts of (s, mu) with the axis and the midpoint line of sight, on uniform rows')
+    ap.add_argument('--velocity', action='store_true',
+                    help='only the velocity kernels against the weighted pair counts of the same rows and edges, on uniform rows')
     args = ap.parse_args()
     be = backend.get()
     dev = be.device
@@ -201,8 +253,8 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1)
         pm = ParticleMesh([args.mesh] * 3, BoxSize=1.0, dtype='f8')
         pos = torch.rand((rows, 3), generator=gen, device=dev, dtype=torch.float64)
-        if args.survey:
-            survey_probe(pm, pos, args)
+        if args.survey or args.velocity:
+            (survey_probe if args.survey else velocity_probe)(pm, pos, args)
             del pos
             torch.cuda.empty_cache()
             continue
