@@ -1088,7 +1088,41 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *             exchanging the two rows, so one set passed as both counts every unordered pair twice, in the numerator
  *             and in the denominator alike.
  *   limit     nr * nsub <= PMX_PAIRS_VELOCITY_MAX_BINS, else PMX_EINVAL: the histogram of a workgroup holds a 32-bit
- *             count and five doubles per bin in LDS (pmx_pairs_vel.hip). */
+ *             count and five doubles per bin in LDS (pmx_pairs_vel.hip).
+ *
+ * The modes by row labels (the one-halo / two-halo split of the pairs, halotools' tpcf_one_two_halo_decomp, and the sums
+ * of a delete-one jackknife over regions, halotools' tpcf_jackknife and pycorr's jackknife estimators;
+ * pmesh_amd.pairlabels).  They are flag bits above the base modes: the valid modes are PMX_PAIRS_SPLIT | m (16 .. 20)
+ * and PMX_PAIRS_JACKKNIFE | m (32 .. 36), m one of the base modes PMX_PAIRS_1D, PMX_PAIRS_2D, PMX_PAIRS_PROJECTED,
+ * PMX_PAIRS_2D_MIDPOINT and PMX_PAIRS_PROJECTED_MIDPOINT; 10 to 15, 21 to 31, 37 and above are PMX_EINVAL.
+ *   shared    rows, wrapping, the minimum image, r2, q, the squared edges, the r-, mu- and pi-bin and the pimax cut are
+ *             exactly those of the base mode m, with its ndim (1 to 3 for 1D, three dimensions otherwise), its los and
+ *             its sub; all arithmetic in double, every operation rounded once, no contraction, no square root choosing
+ *             a bin.  Summed over its label classes, npairs of a label mode equals npairs of the base mode on the same
+ *             arguments, to the last count.
+ *   columns   weight1 and weight2 are both required: pmx_vecs of 2 columns, (w, label), float or double, in ROW order,
+ *             read through order1 / order2.  A wrong ncol, or a missing vec, is PMX_EINVAL.  A label is a non-negative
+ *             integer value held exactly in the column's type.  A label that is negative, not finite, or out of range
+ *             for the call is "no label": the kernel tests it with a comparison that is false for NaN; such a row never
+ *             indexes anything and is never "the same" as any row.
+ *   PMX_PAIRS_SPLIT, nbins = nr * nsub <= 1024, else PMX_EINVAL.  With kind = (a == c and a is a label) ? 1 : 0, per
+ *             counted pair of weight w = w1_i * w2_j in bin b: npairs[kind * nbins + b] += 1, wnpairs[...] += w,
+ *             rsum[...] += w * sqrt(q).  All three arrays have 2 * nbins entries.
+ *   PMX_PAIRS_JACKKNIFE, K = (PMX_PAIRS_LABEL_SLOTS / nbins - 2) / 2 in integer division; K >= 1 is required, that is
+ *             nbins <= 1024, else PMX_EINVAL.  A label is in range when it is below K.  K is fixed by nbins alone: the
+ *             entry needs no further parameter and cannot be handed arrays that are too short.  npairs and wnpairs have
+ *             (1 + 2 K) * nbins entries, in blocks of nbins: block 0 is `all`, block 1 + k is side[k], block 1 + K + k
+ *             is same[k].  rsum has nbins entries and covers `all` only.  Per counted pair in bin b, with labels a
+ *             (primary) and c (secondary): all[b] gets (1, w, w sqrt(q)); if a is in range, side[a][b] gets (1, w); if c
+ *             is in range, side[c][b] gets (1, w), so a pair with a == c adds 2 and 2w (w + w, exact); if a == c and in
+ *             range, same[a][b] gets (1, w).
+ *   sums      all arrays are added to, never overwritten.  npairs is exact and depends on no decomposition or launch.
+ *             The order of the double sums is unspecified, as in the base modes.
+ *   self      the entry knows no row identity.  A self pair has r2 == 0 and a == c, and the caller removes it, as in the
+ *             base modes: from kind 1 (from kind 0 for a row without a label); from all, twice from side[a] and once
+ *             from same[a].
+ *   LDS       the histogram of a workgroup holds a 32-bit count and one double per slot over PMX_PAIRS_LABEL_SLOTS
+ *             slots (pmx_pairs_labels.hip): the "- 2" in K pays for the block of `all` and for its r-sum. */
 #define PMX_PAIRS_MAX_BINS 4096         /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
@@ -1102,6 +1136,9 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
 #define PMX_PAIRS_PROJECTED_VELOCITY 8   /* bins of (rp, pi) about the axis los; line-of-sight pairwise velocity */
 #define PMX_PAIRS_1D_LOS 9               /* bins of r; one line-of-sight scalar per row, observer at the box centre */
 #define PMX_PAIRS_VELOCITY_MAX_BINS 1024 /* nr * nsub of one call in these three modes */
+#define PMX_PAIRS_SPLIT      16   /* | base mode 0..4: pairs apart by "same label" / "not" */
+#define PMX_PAIRS_JACKKNIFE  32   /* | base mode 0..4: all pairs, and per label those touching it and those inside it */
+#define PMX_PAIRS_LABEL_SLOTS 4096
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
@@ -1117,7 +1154,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * midpoint modes, whose kernels (pmx_pairs_survey.hip) are launched from this entry like the others, as are those of
  * the two row modes (pmx_pairs_rows.hip), whose three arrays have n1 * nr * nsub entries, and those of the three
  * velocity modes (pmx_pairs_vel.hip), whose weight1 / weight2 have 1 + ndim or 2 columns and whose rsum has
- * 4 * nr * nsub entries.
+ * 4 * nr * nsub entries, and those of the modes by row labels (pmx_pairs_labels.hip), whose weight1 / weight2 have 2
+ * columns and whose arrays have the lengths given above.
  * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
  * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
  * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)

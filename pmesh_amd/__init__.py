@@ -21,6 +21,9 @@
     from pmesh_amd.knn import knn, knn_density, knn_cdf             # k-nearest-neighbour distances, densities and the kNN-CDF
     from pmesh_amd.profiles import radial_profiles, so_masses      # per-centre radial profiles, Sigma(R) and spherical-overdensity masses
     from pmesh_amd.pairvel import pairwise_velocities, pairwise_los   # pairwise velocities v12(r), their dispersions, v_los(rp, pi); the kSZ pairwise estimator
+    from pmesh_amd.pairlabels import pair_counts_jackknife, pair_correlation_jackknife   # delete-one jackknife counts, xi and its covariance in one walk over the pairs
+    from pmesh_amd.pairlabels import survey_pair_counts_jackknife, survey_correlation_jackknife   # the same about an observer
+    from pmesh_amd.pairlabels import pair_counts_split, pair_correlation_split, box_regions   # the one-halo / two-halo split; sub-box labels
     from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
     from pmesh_amd.lpt import lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp   # and their gradients
 

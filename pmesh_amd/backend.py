@@ -497,7 +497,10 @@ class HipBackend(object):
         on the device; sub: the nsub + 1 squared mu edges or pi edges on the device, None in the mode 1D; weight1 /
         weight2: (n,) or (n, 1) float tensors in row order, or None (pmx_pair_counts).  In the three velocity modes
         (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY, PMX_PAIRS_1D_LOS) weight1 / weight2 are the (n, 1 + ndim)
-        or (n, 2) blocks of columns of the two sets and `rsum` has 4 * nr * nsub entries"""
+        or (n, 2) blocks of columns of the two sets and `rsum` has 4 * nr * nsub entries.  In the modes by row labels
+        (PMX_PAIRS_SPLIT | m, PMX_PAIRS_JACKKNIFE | m) they are the (n, 2) blocks (w, label), and `npairs` and `wnpairs`
+        have 2 (split) or 1 + 2 K (jackknife, K = (PMX_PAIRS_LABEL_SLOTS / nbins - 2) / 2) blocks of nbins entries,
+        `rsum` 2 or 1"""
         if spos1.shape[0] == 0 or spos2.shape[0] == 0:
             return
         if int(mode) in (_abi.PMX_PAIRS_1D_VELOCITY, _abi.PMX_PAIRS_PROJECTED_VELOCITY, _abi.PMX_PAIRS_1D_LOS):
@@ -507,6 +510,20 @@ class HipBackend(object):
             for w, s in ((weight1, spos1), (weight2, spos2)):
                 if w is None or w.dim() != 2 or w.shape[0] != s.shape[0]:
                     raise ValueError('the velocity modes need weight1 and weight2 as (n, ncol) blocks of the rows')
+        split, jack = int(mode) & ~7 == _abi.PMX_PAIRS_SPLIT, int(mode) & ~7 == _abi.PMX_PAIRS_JACKKNIFE
+        if split or jack:
+            # the modes by row labels: (n, 2) blocks (w, label); 2 or 1 + 2 K blocks of nbins entries (rsum: 2 or 1)
+            nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
+            K = (_abi.PMX_PAIRS_LABEL_SLOTS // nbins - 2) // 2
+            if K < 1:
+                raise ValueError('the modes by row labels take at most %d bins' % (_abi.PMX_PAIRS_LABEL_SLOTS // 4))
+            ncount, nrsum = (2 * nbins, 2 * nbins) if split else ((1 + 2 * K) * nbins, nbins)
+            if min(npairs.numel(), wnpairs.numel()) < ncount or rsum.numel() < nrsum:
+                raise ValueError('the modes by row labels need npairs and wnpairs of %d entries and rsum of %d here'
+                                 % (ncount, nrsum))
+            for w, s in ((weight1, spos1), (weight2, spos2)):
+                if w is None or w.dim() != 2 or w.shape[0] != s.shape[0] or w.shape[1] != 2:
+                    raise ValueError('the modes by row labels need weight1 and weight2 as (n, 2) blocks (w, label)')
         wv1, wv2 = _arrays.vec(weight1), _arrays.vec(weight2)
         self.call('pair_counts', spos1.shape[1], int(mode), int(los), spos1.shape[0], spos1.data_ptr(),
                   order1.data_ptr(), cell_of1.data_ptr(), C.byref(wv1) if weight1 is not None else None,

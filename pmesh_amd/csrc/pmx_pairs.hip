@@ -22,7 +22,8 @@
 // have their kernels in pmx_pairs_survey.hip and are launched from pmx_pair_counts below, and so are the modes with one
 // histogram per primary row (PMX_PAIRS_1D_ROWS, PMX_PAIRS_PROJECTED_ROWS), whose kernels are in pmx_pairs_rows.hip, and
 // the modes with pairwise velocity sums (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY, PMX_PAIRS_1D_LOS), whose
-// kernels are in pmx_pairs_vel.hip.
+// kernels are in pmx_pairs_vel.hip, and the modes by row labels (PMX_PAIRS_SPLIT | m, PMX_PAIRS_JACKKNIFE | m), whose
+// kernels are in pmx_pairs_labels.hip.
 #include "pmx_pairs_dev.h"
 
 namespace pmx {
@@ -116,6 +117,11 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     PArgs a;
     const int rc = fof_geom(ndim, boxsize, nullptr, nullptr, ncell, periodic, a.g, &a.ncells);
     if (rc != PMX_OK) return rc;
+    // the modes by row labels: one of the two flags above a base mode 0 .. 4, which says how the pair is binned
+    const bool labels = (mode == (PMX_PAIRS_SPLIT | (mode & 7)) || mode == (PMX_PAIRS_JACKKNIFE | (mode & 7))) &&
+                        (mode & 7) <= PMX_PAIRS_PROJECTED_MIDPOINT;
+    const int entry_mode = mode;
+    if (labels) mode &= 7;
     const bool midpoint = mode == PMX_PAIRS_2D_MIDPOINT || mode == PMX_PAIRS_PROJECTED_MIDPOINT;
     const bool rows = mode == PMX_PAIRS_1D_ROWS || mode == PMX_PAIRS_PROJECTED_ROWS;
     const bool vel = mode == PMX_PAIRS_1D_VELOCITY || mode == PMX_PAIRS_PROJECTED_VELOCITY || mode == PMX_PAIRS_1D_LOS;
@@ -133,6 +139,8 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
                 "more than PMX_PAIRS_ROWS_MAX_BINS bins per row");
     PMX_REQUIRE(!vel || (int64_t)nr * nsub <= PMX_PAIRS_VELOCITY_MAX_BINS, PMX_EINVAL,
                 "more than PMX_PAIRS_VELOCITY_MAX_BINS bins");
+    PMX_REQUIRE(!labels || (int64_t)nr * nsub <= PMX_PAIRS_LABEL_SLOTS / 4, PMX_EINVAL,
+                "more than PMX_PAIRS_LABEL_SLOTS / 4 bins in a mode by row labels");
     PMX_REQUIRE(n1 >= 0 && n2 >= 0, PMX_EINVAL, "bad arguments");
     PMX_REQUIRE(n1 <= PMX_FOF_MAX_ROWS && n2 <= PMX_FOF_MAX_ROWS, PMX_EUNSUPPORTED,
                 "more than 2^31 - 1 rows: slots are 32-bit");
@@ -146,6 +154,8 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     const int32_t vcol = mode == PMX_PAIRS_1D_LOS ? 2 : 1 + ndim;
     PMX_REQUIRE(!vel || (has1 && has2 && weight1->ncol == vcol && weight2->ncol == vcol), PMX_EINVAL,
                 "the velocity modes need weight1 and weight2 of 1 + ndim columns (1D_LOS: 2)");
+    PMX_REQUIRE(!labels || (has1 && has2 && weight1->ncol == 2 && weight2->ncol == 2), PMX_EINVAL,
+                "the modes by row labels need weight1 and weight2 of 2 columns (w, label)");
     a.n1 = n1;
     a.n2 = n2;
     a.spos1 = spos1;
@@ -170,7 +180,8 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     for (int64_t lo = 0; lo < n2; lo += PAIRS_WINDOW) {
         a.slo = (int32_t)lo;
         a.shi = (int32_t)(lo + PAIRS_WINDOW < n2 ? lo + PAIRS_WINDOW : n2);
-        if (midpoint) pairs_survey_launch(a, mode, has1 || has2, grid, st);
+        if (labels) pairs_labels_launch(a, ndim, entry_mode, grid, st);
+        else if (midpoint) pairs_survey_launch(a, mode, has1 || has2, grid, st);
         else if (rows) pairs_rows_launch(a, ndim, mode, has1 || has2, st);
         else if (vel) pairs_vel_launch(a, ndim, mode, grid, st);
         else if (mode == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, has1 || has2, grid, st);

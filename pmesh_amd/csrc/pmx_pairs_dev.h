@@ -152,4 +152,9 @@ void pairs_rows_launch(const PArgs &a, int ndim, int mode, bool weighted, hipStr
 // w2 hold the 1 + ndim or 2 columns of the two sets, rsum has 4 * nbins entries)
 void pairs_vel_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
 
+// pmx_pairs_labels.hip: the launch of one window of the secondaries in the modes PMX_PAIRS_SPLIT | m and
+// PMX_PAIRS_JACKKNIFE | m, m a base mode (pmx_pair_counts has checked the arguments and filled `a`: w1 and w2 hold the
+// columns (w, label) of the two sets, nbins <= PMX_PAIRS_LABEL_SLOTS / 4, the arrays have the lengths of the header)
+void pairs_labels_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
+
 }  // namespace pmx

@@ -61,6 +61,28 @@ KERNEL_MODES = dict(MODES, **{'2d-midpoint': _abi.PMX_PAIRS_2D_MIDPOINT,
 VELOCITY_MODES = {'1d-velocity': _abi.PMX_PAIRS_1D_VELOCITY, 'projected-velocity': _abi.PMX_PAIRS_PROJECTED_VELOCITY,
                   '1d-los': _abi.PMX_PAIRS_1D_LOS}
 KERNEL_MODES.update(VELOCITY_MODES)
+# and those of pmesh_amd.pairlabels, a flag above one of the five base modes: the sets bring the block (w, label), and
+# the three arrays hold 2 (split) or 1 + 2 K (jackknife; rsum: 1) blocks of nbins entries
+LABEL_SLOTS = _abi.PMX_PAIRS_LABEL_SLOTS
+LABEL_BASES = ('1d', '2d', 'projected', '2d-midpoint', 'projected-midpoint')
+LABEL_MODES = {}
+for _family, _flag in (('split', _abi.PMX_PAIRS_SPLIT), ('jackknife', _abi.PMX_PAIRS_JACKKNIFE)):
+    for _base in LABEL_BASES:
+        LABEL_MODES['%s-%s' % (_family, _base)] = _flag | KERNEL_MODES[_base]
+KERNEL_MODES.update(LABEL_MODES)
+
+
+def label_slots(nbins):
+    """K of the jackknife modes: the labels one call takes, ``(PMX_PAIRS_LABEL_SLOTS / nbins - 2) / 2``; below 1: too
+    many bins"""
+    return (LABEL_SLOTS // nbins - 2) // 2
+
+
+def label_lengths(mode, nbins):
+    """the lengths of (npairs and wnpairs, rsum) in a mode of LABEL_MODES"""
+    if mode.startswith('split'):
+        return 2 * nbins, 2 * nbins
+    return (1 + 2 * label_slots(nbins)) * nbins, nbins
 
 
 class PairCounts(object):
@@ -153,12 +175,18 @@ def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub
     every row of `pos2` (None: with every row of pos1, itself included: the caller subtracts the self pairs).  e2 and
     sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat.  In the modes of
     VELOCITY_MODES weight1 and weight2 are the (n, ncol) blocks of columns of the two sets and rsum has 4 * nbins
-    entries, rsum[m * nbins + b]."""
+    entries, rsum[m * nbins + b].  In the modes of LABEL_MODES they are the (n, 2) blocks (w, label) and the arrays have
+    the lengths of label_lengths: the blocks of the header, each of nbins entries."""
     dev = pos1.device
     nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
-    npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
-    wnpairs = torch.zeros(nbins, dtype=torch.float64, device=dev)
-    rsum = torch.zeros(4 * nbins if mode in VELOCITY_MODES else nbins, dtype=torch.float64, device=dev)
+    ncount, nrsum = nbins, 4 * nbins if mode in VELOCITY_MODES else nbins
+    if mode in LABEL_MODES:
+        if label_slots(nbins) < 1:
+            raise ValueError('%d bins: at most %d in the modes by row labels' % (nbins, LABEL_SLOTS // 4))
+        ncount, nrsum = label_lengths(mode, nbins)
+    npairs = torch.zeros(ncount, dtype=torch.int64, device=dev)
+    wnpairs = torch.zeros(ncount, dtype=torch.float64, device=dev)
+    rsum = torch.zeros(nrsum, dtype=torch.float64, device=dev)
     _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
     if pos2 is None:
         order2, cell_start2, spos2, weight2 = order1, cell_start1, spos1, weight1
@@ -188,7 +216,8 @@ def _block_of(weight, cols):
     return torch.cat([w.reshape(-1, 1), cols.to(dtype)], dim=1).contiguous()
 
 
-def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None, columns=None):
+def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None, columns=None,
+           self_pairs=True):
     """What the public counting calls share behind their own reading of the binning: the argument checks of the rows
     and the weights, the weight sums, the routing on one rank or several, the allreduce and the self pairs.
 
@@ -200,6 +229,10 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         sets, (n, ncol) float rows called `name`1 and `name`2 in messages; x2 is given exactly when pos2 is.  They must
         be finite.  Each set then travels as one contiguous (n, 1 + ncol) block (w, columns), w = 1 without a weight,
         float32 where all of its parts are, through the exchanges of the weights, and rsum has 4 * nbins entries.
+        The modes of LABEL_MODES bring ('label', l1, l2, 1) in the same way: the labels as floats, which hold them
+        exactly.
+    self_pairs : False leaves the self pairs of the auto form in the arrays: the caller of a mode of LABEL_MODES, whose
+        arrays hold several blocks, removes them from the blocks they sit in.
     Returns (npairs, wnpairs, rsum: flat device tensors, identical on every rank; W1, W2, W2sum; box)."""
     be = backend.get()
     comm = pm.comm
@@ -277,7 +310,7 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         sums = local_counts(be, kernel, los, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
         sums = [_allsum(comm, s) for s in sums]
     npairs, wnpairs, rsum = sums
-    if auto and first == 0:
+    if self_pairs and auto and first == 0:
         # the self pairs: r2 == 0 exactly, bin (0, 0)
         npairs[0] -= csize1
         wnpairs[0] -= W2sum

@@ -22,9 +22,14 @@ auto counts with 40 bins of r and with 40 x 25 bins of (rp, pi) by the weighted 
 PMX_PAIRS_PROJECTED) and by the velocity kernels of csrc/pmx_pairs_vel.hip (PMX_PAIRS_1D_VELOCITY,
 PMX_PAIRS_PROJECTED_VELOCITY): the kernel times by HIP events, the median of --reps, and their ratios.  One JSON line
 per --rows and b.
+With --labels, instead: the uniform rows with uniform weights and the sub-box labels of box_regions, and on the same
+sorted rows the auto counts with 40 bins of r by the weighted pair-count kernel (PMX_PAIRS_1D) and by the kernels of
+csrc/pmx_pairs_labels.hip: the split with 125 labels, the jackknife with 50 labels (one call) and with 125 (three calls):
+the kernel times by HIP events, the median of --reps, their ratios to one weighted call and to the nlab + 1 weighted
+calls that a jackknife by 0 / 1 weights takes.  One JSON line per --rows and b.
 
     python scripts/pairs_probe.py [--rows 1000000 10000000] [--mesh 256] [--seps 0.5 2 8] [--reps 3]
-                                  [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey] [--velocity]
+                                  [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey] [--velocity] [--labels]
 Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/pairs_probe.py ...` (a run of its
 own).
 """
@@ -233,6 +238,65 @@ def velocity_probe(pm, pos, args):
         torch.cuda.empty_cache()
 
 
+def labels_probe(pm, pos, args):
+    """--labels: the uniform rows with uniform weights and the labels of box_regions, auto, 40 bins of r, on the same
+    sorted rows: the weighted pair-count kernel (PMX_PAIRS_1D), the split kernel with 125 labels and the jackknife kernel
+    of csrc/pmx_pairs_labels.hip with 50 labels (5 x 5 x 2 sub-boxes: one call, K = 50 at 40 bins) and with 125 (5 x 5
+    x 5: three calls, the labels of each chunk shifted to [0, 50) and the others -1, as pair_counts_jackknife makes
+    them): the kernel times, their ratios to one weighted call, and the nlab + 1 weighted calls the jackknife replaces"""
+    from pmesh_amd.pairlabels import box_regions
+    be = backend.get()
+    dev = be.device
+    n = pos.shape[0]
+    box = [float(x) for x in pm.BoxSize]
+    sep = (float(numpy.prod(box)) / n) ** (1.0 / 3)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    w = 0.5 + torch.rand(n, generator=gen, device=dev, dtype=torch.float64)
+    K = (_abi.PMX_PAIRS_LABEL_SLOTS // 40 - 2) // 2
+
+    def block(label, lo=None):
+        if lo is not None:
+            label = torch.where((label >= lo) & (label < lo + K), label - lo, torch.full_like(label, -1))
+        return torch.stack([w, label.to(torch.float64)], dim=1).contiguous()
+    lab50, lab125 = box_regions(pm, pos, [5, 5, 2]), box_regions(pm, pos, 5)
+    for mult in args.seps:
+        b = mult * sep
+        if 2 * b > min(box):
+            continue
+        grid = cell_grid(n, b, box)
+        _, cell_of, cell_start, order, spos, _ = cell_sort(be, pos, grid, box)
+        line = {'input': 'uniform', 'rows': n, 'b_in_mean_separations': mult, 'b': b, 'bins': 40, 'K': K,
+                'cells': int(numpy.prod(grid[0]))}
+        e2 = torch.from_numpy(numpy.linspace(0.0, b, 41) ** 2).to(dev)
+        ncount = (1 + 2 * K) * 40
+        npairs = torch.zeros(ncount, dtype=torch.int64, device=dev)
+        wn = torch.zeros(ncount, dtype=torch.float64, device=dev)
+        rs = torch.zeros(ncount, dtype=torch.float64, device=dev)
+
+        def zero():
+            npairs.zero_(), wn.zero_(), rs.zero_()
+
+        def kernel_ms(mode, weight):
+            return timed(lambda: be.pair_counts(mode, 2, spos, order, cell_of, weight, spos, order, cell_start, weight,
+                                                grid[0], grid[3], box, e2, None, npairs, wn, rs), args.reps, prep=zero)
+        base = kernel_ms(_abi.PMX_PAIRS_1D, w)
+        line['weighted_kernel_ms'] = round(base, 3)
+        line['pairs_counted'] = int(npairs[:40].sum()) - n
+        line['split_kernel_ms'] = round(kernel_ms(_abi.PMX_PAIRS_SPLIT | _abi.PMX_PAIRS_1D, block(lab125)), 3)
+        line['split_over_weighted'] = round(line['split_kernel_ms'] / base, 3)
+        for nlab, lab in ((50, lab50), (125, lab125)):
+            calls = [kernel_ms(_abi.PMX_PAIRS_JACKKNIFE | _abi.PMX_PAIRS_1D, block(lab, lo)) for lo in range(0, nlab, K)]
+            key = 'jackknife%d' % nlab
+            line[key + '_calls'] = len(calls)
+            line[key + '_kernel_ms'] = round(sum(calls), 3)
+            line[key + '_call_over_weighted'] = round(max(calls) / base, 3)
+            line[key + '_weighted_calls_replaced_ms'] = round((nlab + 1) * base, 3)
+            line[key + '_speedup'] = round((nlab + 1) * base / sum(calls), 2)
+        print(json.dumps(line), flush=True)
+        del cell_of, cell_start, order, spos
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, nargs='+', default=[10 ** 6, 10 ** 7])
@@ -246,6 +310,8 @@ def main():
                     help='only the 40 x 100 counts of (s, mu) with the axis and the midpoint line of sight, on uniform rows')
     ap.add_argument('--velocity', action='store_true',
                     help='only the velocity kernels against the weighted pair counts of the same rows and edges, on uniform rows')
+    ap.add_argument('--labels', action='store_true',
+                    help='only the split and jackknife kernels against the weighted pair counts of the same rows and edges, on uniform rows')
     args = ap.parse_args()
     be = backend.get()
     dev = be.device
@@ -253,8 +319,8 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1)
         pm = ParticleMesh([args.mesh] * 3, BoxSize=1.0, dtype='f8')
         pos = torch.rand((rows, 3), generator=gen, device=dev, dtype=torch.float64)
-        if args.survey or args.velocity:
-            (survey_probe if args.survey else velocity_probe)(pm, pos, args)
+        if args.survey or args.velocity or args.labels:
+            (survey_probe if args.survey else velocity_probe if args.velocity else labels_probe)(pm, pos, args)
             del pos
             torch.cuda.empty_cache()
             continue
