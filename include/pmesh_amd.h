@@ -1094,7 +1094,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * of a delete-one jackknife over regions, halotools' tpcf_jackknife and pycorr's jackknife estimators;
  * pmesh_amd.pairlabels).  They are flag bits above the base modes: the valid modes are PMX_PAIRS_SPLIT | m (16 .. 20)
  * and PMX_PAIRS_JACKKNIFE | m (32 .. 36), m one of the base modes PMX_PAIRS_1D, PMX_PAIRS_2D, PMX_PAIRS_PROJECTED,
- * PMX_PAIRS_2D_MIDPOINT and PMX_PAIRS_PROJECTED_MIDPOINT; 10 to 15, 21 to 31, 37 and above are PMX_EINVAL.
+ * PMX_PAIRS_2D_MIDPOINT and PMX_PAIRS_PROJECTED_MIDPOINT; 10 to 15, 21 to 31 and 37 to 127 are PMX_EINVAL, and so is
+ * everything from 128 on but the two alignment modes 128 and 130 described further below.
  *   shared    rows, wrapping, the minimum image, r2, q, the squared edges, the r-, mu- and pi-bin and the pimax cut are
  *             exactly those of the base mode m, with its ndim (1 to 3 for 1D, three dimensions otherwise), its los and
  *             its sub; all arithmetic in double, every operation rounded once, no contraction, no square root choosing
@@ -1122,7 +1123,50 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *             base modes: from kind 1 (from kind 0 for a row without a label); from all, twice from side[a] and once
  *             from same[a].
  *   LDS       the histogram of a workgroup holds a 32-bit count and one double per slot over PMX_PAIRS_LABEL_SLOTS
- *             slots (pmx_pairs_labels.hip): the "- 2" in K pays for the block of `all` and for its r-sum. */
+ *             slots (pmx_pairs_labels.hip): the "- 2" in K pays for the block of `all` and for its r-sum.
+ *
+ * The modes with intrinsic-alignment sums (the position-shape and shape-shape correlations omega(r), eta(r), w_g+(rp)
+ * and w_++(rp): halotools-ia's ed_3d, ee_3d, gi_plus_projected, ii_plus_projected and their minus partners;
+ * pmesh_amd.alignments).  PMX_PAIRS_ALIGN is a flag bit above the base modes: the valid modes are PMX_PAIRS_ALIGN |
+ * PMX_PAIRS_1D (128) and PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED (130); 129, 131, 132, 128 | 16, 128 | 32 and everything
+ * from 133 on are PMX_EINVAL.  Mode 128 shares everything below with PMX_PAIRS_1D, mode 130 with PMX_PAIRS_PROJECTED:
+ *   shared    rows, wrapping, the minimum image dx_d (primary minus secondary), r2, q, the squared edges, the r-bin, the
+ *             pi-bin, the pimax cut and the loop over windows of 2^23 secondaries; all arithmetic in double; every
+ *             operation rounded once, no contraction; no square root chooses a bin.  npairs equals npairs of the base
+ *             mode on the same arguments, to the last count.
+ *   columns   weight1 and weight2 are both required: contiguous pmx_vecs in ROW order, float or double, read through
+ *             order1 / order2.  A wrong ncol, or a missing vec, is PMX_EINVAL.  A set without shapes brings zeros.
+ *   outputs   npairs and wnpairs have nbins = nr * nsub entries.  rsum has (1 + NS) * nbins entries: rsum[m * nbins + b];
+ *             m = 0: sum w sqrt(q), as in the base mode; m = 1 .. NS: the sums below.  All are added to, never
+ *             overwritten.  nbins <= PMX_PAIRS_ALIGN_MAX_BINS, else PMX_EINVAL.  The order of the double sums is
+ *             unspecified; npairs is exact.
+ *   per counted pair, with w = w1_i * w2_j:
+ *   PMX_PAIRS_ALIGN | PMX_PAIRS_1D, ndim 2 or 3 (1 is PMX_EINVAL), nsub == 1, NS = 3.  The columns are (w, a_0 ..
+ *             a_{ndim-1}): an orientation vector, not necessarily a unit vector.  With a the primary's vector and c the
+ *             secondary's, each sum over d < ndim in ascending d: a2 = sum a_d a_d, c2 = sum c_d c_d, pa = sum dx_d a_d,
+ *             pc = sum dx_d c_d, ac = sum a_d c_d.
+ *             t1 = (r2 > 0 && a2 > 0) ? (pa * pa) / (a2 * r2) : 0: cos^2 between the primary's axis and the separation.
+ *             t2 = (r2 > 0 && c2 > 0) ? (pc * pc) / (c2 * r2) : 0.
+ *             t3 = (r2 > 0 && a2 > 0 && c2 > 0) ? (ac * ac) / (a2 * c2) : 0: cos^2 between the two axes.
+ *             S1 += w * t1, S2 += w * t2, S3 += w * t3
+ *   PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED, ndim 3, los in {0, 1, 2}, sub = piedges, NS = 6.  The columns are (w, g1, g2):
+ *             the spin-2 ellipticity in the plane normal to los, referred to the axes A < B, the two axes other than
+ *             los in ascending order; g1 > 0 is elongation along A, g2 > 0 along the diagonal A = B.  With rp2 = q:
+ *             cc = dx_A * dx_A - dx_B * dx_B, ss = 2.0 * (dx_A * dx_B).
+ *             p1 = rp2 > 0 ? (g1_i * cc + g2_i * ss) / rp2 : 0, x1 = rp2 > 0 ? (g1_i * ss - g2_i * cc) / rp2 : 0 for the
+ *             primary; p2 and x2 the same with the secondary's columns (the direction is spin-2: the reversed
+ *             separation gives the same cc and ss).
+ *             S1 += w * p1, S2 += w * p2, S3 += (w * p1) * p2, S4 += (w * x1) * x2, S5 += w * x1, S6 += w * x2
+ *             p > 0: the shape points along the projected separation (radial alignment); x is the 45 degree
+ *             component, whose means vanish by parity.  No trigonometric call and no square root beyond the base
+ *             mode's.
+ *   self      a pair with r2 == 0 (rp2 == 0) adds nothing to S1 .. S_NS: a self pair (one set passed as both) is inert
+ *             there, and the caller subtracts it from npairs[0] and wnpairs[0] as in the base modes.
+ *   scaling   a vector scaled by a power of two changes no bit of any sum of mode 128, and neither does a -> -a.  The
+ *             products a2 * r2 and a2 * c2 must neither overflow nor underflow: finite, sanely scaled columns are the
+ *             caller's business.
+ *   LDS       the histogram of a workgroup holds a 32-bit count and 2 + NS doubles per bin (pmx_pairs_align.hip): 44 KB
+ *             in mode 128, 68 KB in mode 130 at PMX_PAIRS_ALIGN_MAX_BINS bins. */
 #define PMX_PAIRS_MAX_BINS 4096         /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
@@ -1139,6 +1183,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
 #define PMX_PAIRS_SPLIT      16   /* | base mode 0..4: pairs apart by "same label" / "not" */
 #define PMX_PAIRS_JACKKNIFE  32   /* | base mode 0..4: all pairs, and per label those touching it and those inside it */
 #define PMX_PAIRS_LABEL_SLOTS 4096
+#define PMX_PAIRS_ALIGN      128  /* | PMX_PAIRS_1D (128) or PMX_PAIRS_PROJECTED (130): intrinsic-alignment sums */
+#define PMX_PAIRS_ALIGN_MAX_BINS 1024    /* nr * nsub of one call in these two modes */
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.
@@ -1155,7 +1201,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * the two row modes (pmx_pairs_rows.hip), whose three arrays have n1 * nr * nsub entries, and those of the three
  * velocity modes (pmx_pairs_vel.hip), whose weight1 / weight2 have 1 + ndim or 2 columns and whose rsum has
  * 4 * nr * nsub entries, and those of the modes by row labels (pmx_pairs_labels.hip), whose weight1 / weight2 have 2
- * columns and whose arrays have the lengths given above.
+ * columns and whose arrays have the lengths given above, and those of the two alignment modes (pmx_pairs_align.hip),
+ * whose weight1 / weight2 have 1 + ndim or 3 columns and whose rsum has 4 or 7 times nr * nsub entries.
  * The bins are accumulated in a histogram per workgroup in LDS (32-bit counts, double sums); a workgroup makes one global
  * atomic per array and non-zero bin at its end, never one per pair.  No workgroup is given more than 2^31 pairs per
  * launch: above 2^23 secondaries the entry launches once per window of 2^23 slots of the secondaries.  Reads 8 ndim + 8 bytes per slot of the primaries and 8 ndim (+ 4 + elsize with weights)

@@ -24,6 +24,8 @@
     from pmesh_amd.pairlabels import pair_counts_jackknife, pair_correlation_jackknife   # delete-one jackknife counts, xi and its covariance in one walk over the pairs
     from pmesh_amd.pairlabels import survey_pair_counts_jackknife, survey_correlation_jackknife   # the same about an observer
     from pmesh_amd.pairlabels import pair_counts_split, pair_correlation_split, box_regions   # the one-halo / two-halo split; sub-box labels
+    from pmesh_amd.alignments import alignment_counts, projected_alignment_counts   # intrinsic alignments: omega(r), eta(r), w_g+(rp), w_++(rp)
+    from pmesh_amd.alignments import ellipticity_from_orientation   # the projected spin-2 ellipticity of a 3-d axis
     from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
     from pmesh_amd.lpt import lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp   # and their gradients
 

@@ -500,7 +500,9 @@ class HipBackend(object):
         or (n, 2) blocks of columns of the two sets and `rsum` has 4 * nr * nsub entries.  In the modes by row labels
         (PMX_PAIRS_SPLIT | m, PMX_PAIRS_JACKKNIFE | m) they are the (n, 2) blocks (w, label), and `npairs` and `wnpairs`
         have 2 (split) or 1 + 2 K (jackknife, K = (PMX_PAIRS_LABEL_SLOTS / nbins - 2) / 2) blocks of nbins entries,
-        `rsum` 2 or 1"""
+        `rsum` 2 or 1.  In the two alignment modes (PMX_PAIRS_ALIGN | PMX_PAIRS_1D, PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED)
+        they are the (n, 1 + ndim) blocks (w, a) or the (n, 3) blocks (w, g1, g2), and `rsum` has 4 or 7 times nr * nsub
+        entries"""
         if spos1.shape[0] == 0 or spos2.shape[0] == 0:
             return
         if int(mode) in (_abi.PMX_PAIRS_1D_VELOCITY, _abi.PMX_PAIRS_PROJECTED_VELOCITY, _abi.PMX_PAIRS_1D_LOS):
@@ -510,6 +512,15 @@ class HipBackend(object):
             for w, s in ((weight1, spos1), (weight2, spos2)):
                 if w is None or w.dim() != 2 or w.shape[0] != s.shape[0]:
                     raise ValueError('the velocity modes need weight1 and weight2 as (n, ncol) blocks of the rows')
+        if int(mode) in (_abi.PMX_PAIRS_ALIGN | _abi.PMX_PAIRS_1D, _abi.PMX_PAIRS_ALIGN | _abi.PMX_PAIRS_PROJECTED):
+            # the alignment modes: (n, 1 + ndim) or (n, 3) blocks; rsum of 4 or 7 times nbins entries
+            nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
+            nsums = 7 if int(mode) & 7 == _abi.PMX_PAIRS_PROJECTED else 4
+            if rsum.numel() < nsums * nbins or min(npairs.numel(), wnpairs.numel()) < nbins:
+                raise ValueError('the alignment modes need rsum of %d * nr * nsub entries' % nsums)
+            for w, s in ((weight1, spos1), (weight2, spos2)):
+                if w is None or w.dim() != 2 or w.shape[0] != s.shape[0]:
+                    raise ValueError('the alignment modes need weight1 and weight2 as (n, ncol) blocks of the rows')
         split, jack = int(mode) & ~7 == _abi.PMX_PAIRS_SPLIT, int(mode) & ~7 == _abi.PMX_PAIRS_JACKKNIFE
         if split or jack:
             # the modes by row labels: (n, 2) blocks (w, label); 2 or 1 + 2 K blocks of nbins entries (rsum: 2 or 1)

@@ -23,7 +23,8 @@
 // histogram per primary row (PMX_PAIRS_1D_ROWS, PMX_PAIRS_PROJECTED_ROWS), whose kernels are in pmx_pairs_rows.hip, and
 // the modes with pairwise velocity sums (PMX_PAIRS_1D_VELOCITY, PMX_PAIRS_PROJECTED_VELOCITY, PMX_PAIRS_1D_LOS), whose
 // kernels are in pmx_pairs_vel.hip, and the modes by row labels (PMX_PAIRS_SPLIT | m, PMX_PAIRS_JACKKNIFE | m), whose
-// kernels are in pmx_pairs_labels.hip.
+// kernels are in pmx_pairs_labels.hip, and the modes with intrinsic-alignment sums (PMX_PAIRS_ALIGN | PMX_PAIRS_1D,
+// PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED), whose kernels are in pmx_pairs_align.hip.
 #include "pmx_pairs_dev.h"
 
 namespace pmx {
@@ -122,23 +123,30 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
                         (mode & 7) <= PMX_PAIRS_PROJECTED_MIDPOINT;
     const int entry_mode = mode;
     if (labels) mode &= 7;
+    // the modes with alignment sums: the flag PMX_PAIRS_ALIGN above the base mode 1D or projected and nothing else (the
+    // test is on the whole word: `mode & 7` of the label flags above never sees 128 | m as a label mode)
+    const bool align = entry_mode == (PMX_PAIRS_ALIGN | PMX_PAIRS_1D) || entry_mode == (PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED);
+    if (align) mode &= 7;
     const bool midpoint = mode == PMX_PAIRS_2D_MIDPOINT || mode == PMX_PAIRS_PROJECTED_MIDPOINT;
     const bool rows = mode == PMX_PAIRS_1D_ROWS || mode == PMX_PAIRS_PROJECTED_ROWS;
     const bool vel = mode == PMX_PAIRS_1D_VELOCITY || mode == PMX_PAIRS_PROJECTED_VELOCITY || mode == PMX_PAIRS_1D_LOS;
     const bool one = mode == PMX_PAIRS_1D || mode == PMX_PAIRS_1D_ROWS || mode == PMX_PAIRS_1D_VELOCITY ||
-                     mode == PMX_PAIRS_1D_LOS;
+                     mode == PMX_PAIRS_1D_LOS;                       // (align: its base mode)
     PMX_REQUIRE(mode == PMX_PAIRS_1D || mode == PMX_PAIRS_2D || mode == PMX_PAIRS_PROJECTED || midpoint || rows || vel,
                 PMX_EINVAL, "bad mode");
     PMX_REQUIRE(one || midpoint || (ndim == 3 && los >= 0 && los <= 2), PMX_EINVAL,
                 "the modes 2D and projected need three dimensions and a line of sight along one of them");
     PMX_REQUIRE(!midpoint || ndim == 3, PMX_EINVAL, "the midpoint modes need three dimensions");
     PMX_REQUIRE(mode != PMX_PAIRS_1D_LOS || ndim == 3, PMX_EINVAL, "the mode 1D_LOS needs three dimensions");
+    PMX_REQUIRE(!align || ndim == 2 || ndim == 3, PMX_EINVAL, "the alignment modes need two or three dimensions");
     PMX_REQUIRE(nr >= 1 && nsub >= 1 && (!one || nsub == 1), PMX_EINVAL, "bad bin counts");
     PMX_REQUIRE((int64_t)nr * nsub <= PMX_PAIRS_MAX_BINS, PMX_EINVAL, "more than PMX_PAIRS_MAX_BINS bins");
     PMX_REQUIRE(!rows || (int64_t)nr * nsub <= PMX_PAIRS_ROWS_MAX_BINS, PMX_EINVAL,
                 "more than PMX_PAIRS_ROWS_MAX_BINS bins per row");
     PMX_REQUIRE(!vel || (int64_t)nr * nsub <= PMX_PAIRS_VELOCITY_MAX_BINS, PMX_EINVAL,
                 "more than PMX_PAIRS_VELOCITY_MAX_BINS bins");
+    PMX_REQUIRE(!align || (int64_t)nr * nsub <= PMX_PAIRS_ALIGN_MAX_BINS, PMX_EINVAL,
+                "more than PMX_PAIRS_ALIGN_MAX_BINS bins");
     PMX_REQUIRE(!labels || (int64_t)nr * nsub <= PMX_PAIRS_LABEL_SLOTS / 4, PMX_EINVAL,
                 "more than PMX_PAIRS_LABEL_SLOTS / 4 bins in a mode by row labels");
     PMX_REQUIRE(n1 >= 0 && n2 >= 0, PMX_EINVAL, "bad arguments");
@@ -154,6 +162,10 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     const int32_t vcol = mode == PMX_PAIRS_1D_LOS ? 2 : 1 + ndim;
     PMX_REQUIRE(!vel || (has1 && has2 && weight1->ncol == vcol && weight2->ncol == vcol), PMX_EINVAL,
                 "the velocity modes need weight1 and weight2 of 1 + ndim columns (1D_LOS: 2)");
+    // the alignment modes: (w, a_0 .. a_{ndim-1}) above 1D, (w, g1, g2) above projected
+    const int32_t acol = mode == PMX_PAIRS_PROJECTED ? 3 : 1 + ndim;
+    PMX_REQUIRE(!align || (has1 && has2 && weight1->ncol == acol && weight2->ncol == acol), PMX_EINVAL,
+                "the alignment modes need weight1 and weight2 of 1 + ndim columns (projected: 3)");
     PMX_REQUIRE(!labels || (has1 && has2 && weight1->ncol == 2 && weight2->ncol == 2), PMX_EINVAL,
                 "the modes by row labels need weight1 and weight2 of 2 columns (w, label)");
     a.n1 = n1;
@@ -181,6 +193,7 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
         a.slo = (int32_t)lo;
         a.shi = (int32_t)(lo + PAIRS_WINDOW < n2 ? lo + PAIRS_WINDOW : n2);
         if (labels) pairs_labels_launch(a, ndim, entry_mode, grid, st);
+        else if (align) pairs_align_launch(a, ndim, entry_mode, grid, st);
         else if (midpoint) pairs_survey_launch(a, mode, has1 || has2, grid, st);
         else if (rows) pairs_rows_launch(a, ndim, mode, has1 || has2, st);
         else if (vel) pairs_vel_launch(a, ndim, mode, grid, st);

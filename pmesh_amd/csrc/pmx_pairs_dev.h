@@ -157,4 +157,9 @@ void pairs_vel_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStre
 // columns (w, label) of the two sets, nbins <= PMX_PAIRS_LABEL_SLOTS / 4, the arrays have the lengths of the header)
 void pairs_labels_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
 
+// pmx_pairs_align.hip: the launch of one window of the secondaries in the modes PMX_PAIRS_ALIGN | PMX_PAIRS_1D and
+// PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED (pmx_pair_counts has checked the arguments and filled `a`: w1 and w2 hold the
+// 1 + ndim or 3 columns of the two sets, nbins <= PMX_PAIRS_ALIGN_MAX_BINS, rsum has 4 or 7 times nbins entries)
+void pairs_align_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
+
 }  // namespace pmx

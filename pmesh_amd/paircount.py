@@ -70,6 +70,12 @@ for _family, _flag in (('split', _abi.PMX_PAIRS_SPLIT), ('jackknife', _abi.PMX_P
     for _base in LABEL_BASES:
         LABEL_MODES['%s-%s' % (_family, _base)] = _flag | KERNEL_MODES[_base]
 KERNEL_MODES.update(LABEL_MODES)
+# and the two of pmesh_amd.alignments, the flag PMX_PAIRS_ALIGN above the base modes 1d and projected: the sets bring the
+# block (w, a_0 .. a_{ndim-1}) or (w, g1, g2), and rsum holds 1 + NS sums per bin, NS = 3 or 6
+ALIGN_MODES = {'1d-align': _abi.PMX_PAIRS_ALIGN | _abi.PMX_PAIRS_1D,
+               'projected-align': _abi.PMX_PAIRS_ALIGN | _abi.PMX_PAIRS_PROJECTED}
+ALIGN_SUMS = {'1d-align': 3, 'projected-align': 6}
+KERNEL_MODES.update(ALIGN_MODES)
 
 
 def label_slots(nbins):
@@ -176,10 +182,16 @@ def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub
     sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat.  In the modes of
     VELOCITY_MODES weight1 and weight2 are the (n, ncol) blocks of columns of the two sets and rsum has 4 * nbins
     entries, rsum[m * nbins + b].  In the modes of LABEL_MODES they are the (n, 2) blocks (w, label) and the arrays have
-    the lengths of label_lengths: the blocks of the header, each of nbins entries."""
+    the lengths of label_lengths: the blocks of the header, each of nbins entries.  In the modes of ALIGN_MODES they are
+    the (n, 1 + ndim) blocks (w, a) or the (n, 3) blocks (w, g1, g2), and rsum has (1 + NS) * nbins entries, NS of
+    ALIGN_SUMS."""
     dev = pos1.device
     nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
     ncount, nrsum = nbins, 4 * nbins if mode in VELOCITY_MODES else nbins
+    if mode in ALIGN_MODES:
+        if nbins > _abi.PMX_PAIRS_ALIGN_MAX_BINS:
+            raise ValueError('%d bins: at most %d in the alignment modes' % (nbins, _abi.PMX_PAIRS_ALIGN_MAX_BINS))
+        nrsum = (1 + ALIGN_SUMS[mode]) * nbins
     if mode in LABEL_MODES:
         if label_slots(nbins) < 1:
             raise ValueError('%d bins: at most %d in the modes by row labels' % (nbins, LABEL_SLOTS // 4))
@@ -230,7 +242,9 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         be finite.  Each set then travels as one contiguous (n, 1 + ncol) block (w, columns), w = 1 without a weight,
         float32 where all of its parts are, through the exchanges of the weights, and rsum has 4 * nbins entries.
         The modes of LABEL_MODES bring ('label', l1, l2, 1) in the same way: the labels as floats, which hold them
-        exactly.
+        exactly.  The modes of ALIGN_MODES bring ('shape', s1, s2, ndim) or ('ellipticity', g1, g2, 2), and rsum has
+        (1 + NS) * nbins entries.  A fifth member, (bool, bool), says of which of the two sets a row whose columns are
+        all zero is refused (an orientation of no direction): ValueError with their number, on every rank.
     self_pairs : False leaves the self pairs of the auto form in the arrays: the caller of a mode of LABEL_MODES, whose
         arrays hold several blocks, removes them from the blocks they sit in.
     Returns (npairs, wnpairs, rsum: flat device tensors, identical on every rank; W1, W2, W2sum; box)."""
@@ -246,7 +260,7 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         error = ValueError('weight2 needs pos2')
     wanted = [('pos1', pos1, nd, None), ('pos2', pos2, nd, None), ('weight1', weight1, 1, 0), ('weight2', weight2, 1, 1)]
     if columns is not None:
-        name, x1, x2, ncol = columns
+        name, x1, x2, ncol = columns[:4]
         if error is None and x1 is None:
             error = ValueError('%s1 is needed' % name)
         if error is None and (x2 is None) != auto:
@@ -275,6 +289,12 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
             nbad = int(comm.allreduce(nbad))
         if nbad:
             raise ValueError('%d rows of %s1 and %s2 have an entry that is not finite' % (nbad, columns[0], columns[0]))
+        if len(columns) > 4:
+            nbad = sum(int((x == 0).all(dim=1).sum()) for x, on in zip(rows[4:], columns[4]) if x is not None and on)
+            if comm.size > 1:
+                nbad = int(comm.allreduce(nbad))
+            if nbad:
+                raise ValueError('%d rows of %s1 and %s2 are zero vectors' % (nbad, columns[0], columns[0]))
     if prepare is not None:
         pos1, pos2 = prepare(pos1, pos2)
     n1 = pos1.shape[0]
@@ -302,8 +322,12 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         most = max(own.recvlength, ghosts.recvlength)
         _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
         p1 = own.exchange(pos1)
+        # (a layout remembers its last exchange by the address and shape of the tensor: the rows of a rank that holds
+        # none and its block of as many columns, as in the mode projected-align, share both)
+        own.forget()
         q1 = own.exchange(weight1) if weight1 is not None else None
         p2 = ghosts.exchange(pos1 if auto else pos2)
+        ghosts.forget()
         w2 = weight1 if auto else weight2
         q2 = ghosts.exchange(w2) if w2 is not None else None
         lo, hi = _block(pm)

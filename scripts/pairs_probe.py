@@ -27,9 +27,16 @@ sorted rows the auto counts with 40 bins of r by the weighted pair-count kernel 
 csrc/pmx_pairs_labels.hip: the split with 125 labels, the jackknife with 50 labels (one call) and with 125 (three calls):
 the kernel times by HIP events, the median of --reps, their ratios to one weighted call and to the nlab + 1 weighted
 calls that a jackknife by 0 / 1 weights takes.  One JSON line per --rows and b.
+With --align, instead: the uniform rows with uniform weights, normal velocities, normal orientation vectors and the
+ellipticities of those, and on the same sorted rows the auto counts with 40 bins of r and with 40 x 25 bins of (rp, pi)
+by the weighted pair-count kernel, by the matching velocity kernel and by the alignment kernels of
+csrc/pmx_pairs_align.hip (PMX_PAIRS_ALIGN | PMX_PAIRS_1D, PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED), the three launched in
+turn --reps times (3 at least) after one warm-up round: per kernel the median by HIP events and the spread (max - min)
+/ median of its repetitions, and the ratios of the alignment kernel to the other two.  One JSON line per --rows and b.
 
     python scripts/pairs_probe.py [--rows 1000000 10000000] [--mesh 256] [--seps 0.5 2 8] [--reps 3]
                                   [--host-rows 1000000] [--no-host] [--no-lognormal] [--survey] [--velocity] [--labels]
+                                  [--align]
 Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -- python scripts/pairs_probe.py ...` (a run of its
 own).
 """
@@ -297,6 +304,70 @@ def labels_probe(pm, pos, args):
         torch.cuda.empty_cache()
 
 
+def align_probe(pm, pos, args):
+    """--align: the uniform rows with uniform weights, auto, on the same sorted rows and edges: the weighted pair_counts
+    kernel (PMX_PAIRS_1D with 40 bins of r, PMX_PAIRS_PROJECTED with 40 x 25 bins of (rp, pi)), the matching velocity
+    kernel of csrc/pmx_pairs_vel.hip and the alignment kernel of csrc/pmx_pairs_align.hip, launched in turn: the
+    medians, the spread of the repetitions and the ratios"""
+    from pmesh_amd.alignments import ellipticity_from_orientation
+    be = backend.get()
+    dev = be.device
+    n = pos.shape[0]
+    box = [float(x) for x in pm.BoxSize]
+    sep = (float(numpy.prod(box)) / n) ** (1.0 / 3)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    w = 0.5 + torch.rand((n, 1), generator=gen, device=dev, dtype=torch.float64)
+    vel = torch.randn((n, 3), generator=gen, device=dev, dtype=torch.float64)
+    axis = torch.randn((n, 3), generator=gen, device=dev, dtype=torch.float64)
+    blocks = {'weighted': w.reshape(-1).contiguous(), 'velocity': torch.cat([w, vel], dim=1).contiguous(),
+              '1d_align': torch.cat([w, axis], dim=1).contiguous(),
+              'projected_align': torch.cat([w, ellipticity_from_orientation(axis, los=2, magnitude=0.3)], dim=1).contiguous()}
+    reps = max(args.reps, 3)
+    for mult in args.seps:
+        b = mult * sep
+        if 2 * b > min(box):
+            continue
+        grid = cell_grid(n, b, box)
+        _, cell_of, cell_start, order, spos, _ = cell_sort(be, pos, grid, box)
+        line = {'input': 'uniform', 'rows': n, 'b_in_mean_separations': mult, 'b': b, 'cells': int(numpy.prod(grid[0])),
+                'reps': reps}
+        e2 = torch.from_numpy(numpy.linspace(0.0, b, 41) ** 2).to(dev)
+        pie = torch.from_numpy(numpy.linspace(0.0, b, 26)).to(dev)
+        for key, sub, base in (('1d', None, _abi.PMX_PAIRS_1D), ('projected', pie, _abi.PMX_PAIRS_PROJECTED)):
+            nbins = 40 * (1 if sub is None else 25)
+            npairs = torch.zeros(nbins, dtype=torch.int64, device=dev)
+            wn = torch.zeros(nbins, dtype=torch.float64, device=dev)
+            rs = torch.zeros(7 * nbins, dtype=torch.float64, device=dev)
+            kernels = (('weighted', base, blocks['weighted']),
+                       ('velocity', _abi.PMX_PAIRS_1D_VELOCITY if sub is None else _abi.PMX_PAIRS_PROJECTED_VELOCITY,
+                        blocks['velocity']),
+                       ('align', _abi.PMX_PAIRS_ALIGN | base, blocks[key + '_align']))
+            ms = {which: [] for which, _, _ in kernels}
+            for r in range(reps + 1):
+                for which, mode, weight in kernels:
+                    npairs.zero_(), wn.zero_(), rs.zero_()
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    be.pair_counts(mode, 2, spos, order, cell_of, weight, spos, order, cell_start, weight, grid[0],
+                                   grid[3], box, e2, sub, npairs, wn, rs)
+                    t1.record()
+                    t1.synchronize()
+                    if r:
+                        ms[which].append(t0.elapsed_time(t1))
+                    line['%s_%s_pairs_counted' % (key, which)] = int(npairs.sum()) - n
+            for which in ms:
+                med = float(numpy.median(ms[which]))
+                line['%s_%s_kernel_ms' % (key, which)] = round(med, 3)
+                line['%s_%s_spread' % (key, which)] = round((max(ms[which]) - min(ms[which])) / med, 4)
+            line['%s_bins' % key] = nbins
+            for other in ('weighted', 'velocity'):
+                line['%s_align_over_%s' % (key, other)] = round(line['%s_align_kernel_ms' % key] /
+                                                                line['%s_%s_kernel_ms' % (key, other)], 3)
+        print(json.dumps(line), flush=True)
+        del cell_of, cell_start, order, spos
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, nargs='+', default=[10 ** 6, 10 ** 7])
@@ -312,6 +383,8 @@ def main():
                     help='only the velocity kernels against the weighted pair counts of the same rows and edges, on uniform rows')
     ap.add_argument('--labels', action='store_true',
                     help='only the split and jackknife kernels against the weighted pair counts of the same rows and edges, on uniform rows')
+    ap.add_argument('--align', action='store_true',
+                    help='only the alignment kernels in turn with the weighted and the velocity kernels on the same rows and edges, on uniform rows')
     args = ap.parse_args()
     be = backend.get()
     dev = be.device
@@ -319,8 +392,9 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1)
         pm = ParticleMesh([args.mesh] * 3, BoxSize=1.0, dtype='f8')
         pos = torch.rand((rows, 3), generator=gen, device=dev, dtype=torch.float64)
-        if args.survey or args.velocity or args.labels:
-            (survey_probe if args.survey else velocity_probe if args.velocity else labels_probe)(pm, pos, args)
+        if args.survey or args.velocity or args.labels or args.align:
+            (survey_probe if args.survey else velocity_probe if args.velocity else labels_probe if args.labels
+             else align_probe)(pm, pos, args)
             del pos
             torch.cuda.empty_cache()
             continue
