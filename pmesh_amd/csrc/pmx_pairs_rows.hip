@@ -2,9 +2,9 @@
 // PMX_PAIRS_PROJECTED_ROWS of pmx_pair_counts (include/pmesh_amd.h; pmesh_amd/profiles.py).
 //
 // What callers do today with a kd-tree on the host, or with one pair count per centre: the radial profile, the
-// enclosed mass and Sigma(R) of the rows around every centre.  The rule is that of pmx_pairs.hip (double arithmetic,
-// every operation rounded once, squared edges, no square root choosing a bin, exact npairs, double sums in no
-// particular order) with one change: the bin of a pair is (i * nr + rbin) * nsub + subbin, i the ROW of the primary.
+// enclosed mass and Sigma(R) of the rows around every centre.  Which pair is counted and in which bin: pair_rule
+// (pmx_pairs_dev.h), in the base modes 1D and PROJECTED; the sums are those of pmx_pairs.hip, with one change: the bin
+// of a pair is (i * nr + rbin) * nsub + subbin, i the ROW of the primary.
 // The pass: rows_kernel, one wave per slot of the primaries in cell order, four consecutive slots per workgroup (they
 // sit in one cell or in adjacent ones and read the same secondaries from cache), the shape of pmx_knn.hip.  Lane nb
 // reads the range of slots of the nb-th of the 3^ndim neighbouring cells, clipped to the window [slo, shi) of the
@@ -26,7 +26,7 @@
 
 namespace pmx {
 
-constexpr int RBLOCK = PBLOCK;                   // (pair_edges_load strides by PBLOCK)
+constexpr int RBLOCK = PBLOCK;                   // (pair_edges_init strides by PBLOCK)
 constexpr int RWAVES = RBLOCK / 64;              // primaries per workgroup
 constexpr int RSLOTS = PMX_PAIRS_ROWS_MAX_BINS;  // bins x copies of one wave: 4 x 256 x 12 (weighted: 20) bytes = 12 / 20 KB
 constexpr int ROWS_COPIES_MAX = PMX_ROWS_COPIES_MAX;
@@ -34,12 +34,11 @@ constexpr int ROWS_COPIES_MAX = PMX_ROWS_COPIES_MAX;
 template <int NDIM, int MODE, bool WEIGHTED>
 __global__ void __launch_bounds__(RBLOCK) rows_kernel(PArgs a, int copies)
 {
-    constexpr bool PROJECTED = MODE == PMX_PAIRS_PROJECTED_ROWS;
+    constexpr int BASE = MODE == PMX_PAIRS_PROJECTED_ROWS ? PMX_PAIRS_PROJECTED : PMX_PAIRS_1D;
     __shared__ uint32_t hcount[RWAVES][RSLOTS];
     __shared__ double hrsum[RWAVES][RSLOTS];
     __shared__ double hwsum[WEIGHTED ? RWAVES : 1][WEIGHTED ? RSLOTS : 1];
-    __shared__ double se2[PAIRS_EDGES_LDS + 1];
-    __shared__ double ssub[PROJECTED ? PAIRS_EDGES_LDS + 1 : 1];
+    __shared__ PairEdges<BASE> ed;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t *hc = hcount[wave];
     double *hr = hrsum[wave], *hw = hwsum[WEIGHTED ? wave : 0];
@@ -49,38 +48,28 @@ __global__ void __launch_bounds__(RBLOCK) rows_kernel(PArgs a, int copies)
         hr[s] = 0;
         if (WEIGHTED) hw[s] = 0;
     }
-    const bool e_lds = a.nr <= PAIRS_EDGES_LDS, s_lds = a.nsub <= PAIRS_EDGES_LDS;
-    if (e_lds) pair_edges_load(se2, a.e2, a.nr, tid);
-    if (PROJECTED && s_lds) pair_edges_load(ssub, a.sub, a.nsub, tid);
+    pair_edges_init(a, ed, tid);
     __syncthreads();                                             // (the only barrier: every wave has come here)
 
-    const int64_t p = (int64_t)blockIdx.x * RWAVES + wave;
-    if (p >= a.n1) return;                                       // (the whole wave)
-    const int32_t i = a.order1[p];
-    if (i < 0 || i >= a.n1) return;                              // (never, with the order fill_kernel left)
-    const int32_t flat = a.cell_of1[i];
-    if (flat < 0 || flat >= a.ncells) return;                    // (never)
+    PairLane<NDIM> p;                                            // (of the whole wave)
+    if (!pair_lane(a, (int64_t)blockIdx.x * RWAVES + wave, p)) return;
     const FGeom &g = a.g;
-    double x[NDIM], quarter[NDIM];
 #pragma unroll
-    for (int d = 0; d < NDIM; d++) {
-        x[d] = a.spos1[p * NDIM + d];
-        quarter[d] = 0.25 * g.L[d];
-    }
+    for (int d = 0; d < NDIM; d++) p.quarter[d] = 0.25 * g.L[d];   // (here, not in pair_lane: see there)
+    const int32_t i = p.i;
     double w1 = 1.0;
     if (WEIGHTED && a.w1.data) w1 = a.w1.get(i, 0);
-    const double qlo = a.e2[0], qhi = a.e2[a.nr];
-    const double pimax = PROJECTED ? a.sub[a.nsub] : 0.0;
+    const PairLimits lim = pair_limits(a, ed);
     const int copy = lane & (copies - 1);
 
-    int32_t c[3];
-    fof_cell_axes<NDIM>(g, flat, c);
+    pair_lane_cell(a, p);
+
     constexpr int NB = fof_neighbours<NDIM>();
     // lane nb < NB holds the slots of the nb-th neighbouring cell inside the window of this launch
     int32_t first = 0, len = 0;
     if (lane < NB) {
         int32_t cell;
-        if (fof_neighbour<NDIM>(g, c, lane, cell)) {
+        if (fof_neighbour<NDIM>(g, p.c, lane, cell)) {
             const int32_t s0 = max(a.cell_start2[cell], a.slo), s1 = min(a.cell_start2[cell + 1], a.shi);
             if (s1 > s0) {
                 first = s0;
@@ -98,20 +87,14 @@ __global__ void __launch_bounds__(RBLOCK) rows_kernel(PArgs a, int copies)
     const uint32_t total = __shfl(end, 31, 64);
     // one slot s of the secondaries against the row of this wave
     auto visit = [&](int32_t s) {
-        double dx[NDIM], q = 0;
+        double y[NDIM], dx[NDIM], q;
 #pragma unroll
         for (int d = 0; d < NDIM; d++) {
-            dx[d] = pair_image(x[d] - a.spos2[(int64_t)s * NDIM + d], g.L[d], quarter[d]);
-            if (!PROJECTED || d != a.los) q += dx[d] * dx[d];
+            y[d] = a.spos2[(int64_t)s * NDIM + d];
+            dx[d] = pair_image(p.x[d] - y[d], g.L[d], p.quarter[d]);
         }
-        if (!(q >= qlo && q < qhi)) return;
-        int bin = e_lds ? pair_bin(se2, a.nr, q) : pair_bin(a.e2, a.nr, q);
-        if (PROJECTED) {
-            const double az = fabs(a.los == 0 ? dx[0] : (a.los == 1 ? dx[NDIM > 1 ? 1 : 0] : dx[NDIM > 2 ? 2 : 0]));
-            if (!(az < pimax)) return;
-            // (az >= 0 = piedges[0] where the edges are the rule's; anything below the first edge goes to bin 0)
-            bin = bin * a.nsub + (s_lds ? pair_bin(ssub, a.nsub, az) : pair_bin(a.sub, a.nsub, az));
-        }
+        int bin;
+        if (!pair_rule<NDIM>(a, lim, ed, p.x, y, dx, q, bin)) return;
         if (bin < 0 || bin >= a.nbins) return;                   // (never: 0 <= bin < nbins)
         const int slot = bin * copies + copy;
         if (slot >= used) return;                                // (never: copies * nbins <= RSLOTS)

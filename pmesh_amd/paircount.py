@@ -91,6 +91,17 @@ def label_lengths(mode, nbins):
     return (1 + 2 * label_slots(nbins)) * nbins, nbins
 
 
+# every mode of local_counts: (the blocks of nbins entries in npairs and wnpairs, None: the 1 + 2 K of the jackknife;
+# the blocks in rsum; the most bins that local_counts itself checks, None where the callers' check is the only one;
+# what its error calls the modes)
+_BLOCKS = {_mode: (1, 1, None, None) for _mode in KERNEL_MODES}
+_BLOCKS.update({_mode: (1, 4, None, None) for _mode in VELOCITY_MODES})
+_BLOCKS.update({_mode: (2 if _mode.startswith('split') else None, 2 if _mode.startswith('split') else 1,
+                        LABEL_SLOTS // 4, 'the modes by row labels') for _mode in LABEL_MODES})
+_BLOCKS.update({_mode: (1, 1 + ALIGN_SUMS[_mode], _abi.PMX_PAIRS_ALIGN_MAX_BINS, 'the alignment modes')
+                for _mode in ALIGN_MODES})
+
+
 class PairCounts(object):
     """The binned sums over the pairs, identical on every rank: ``npairs`` (int64), ``wnpairs``, ``rsum`` and ``rmean =
     rsum / wnpairs`` (float64; nan where the bin holds no pair), device tensors of the shape (nr,), (nr, nmu) or (nrp,
@@ -187,15 +198,12 @@ def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub
     ALIGN_SUMS."""
     dev = pos1.device
     nbins = (e2.numel() - 1) * (sub.numel() - 1 if sub is not None else 1)
-    ncount, nrsum = nbins, 4 * nbins if mode in VELOCITY_MODES else nbins
-    if mode in ALIGN_MODES:
-        if nbins > _abi.PMX_PAIRS_ALIGN_MAX_BINS:
-            raise ValueError('%d bins: at most %d in the alignment modes' % (nbins, _abi.PMX_PAIRS_ALIGN_MAX_BINS))
-        nrsum = (1 + ALIGN_SUMS[mode]) * nbins
-    if mode in LABEL_MODES:
-        if label_slots(nbins) < 1:
-            raise ValueError('%d bins: at most %d in the modes by row labels' % (nbins, LABEL_SLOTS // 4))
-        ncount, nrsum = label_lengths(mode, nbins)
+    counts, sums, limit, what = _BLOCKS[mode]
+    if limit is not None and nbins > limit:
+        raise ValueError('%d bins: at most %d in %s' % (nbins, limit, what))
+    if counts is None:
+        counts = 1 + 2 * label_slots(nbins)
+    ncount, nrsum = counts * nbins, sums * nbins
     npairs = torch.zeros(ncount, dtype=torch.int64, device=dev)
     wnpairs = torch.zeros(ncount, dtype=torch.float64, device=dev)
     rsum = torch.zeros(nrsum, dtype=torch.float64, device=dev)
