@@ -66,7 +66,7 @@ import numpy
 import torch
 
 from . import _abi, backend
-from .paircount import PairCounts, _binning, _count, bin_volumes
+from .paircount import PairCounts, _binning, _count, bin_volumes, too_many
 from .pairvel import _ratio
 from .surveypairs import to_wp
 
@@ -130,13 +130,6 @@ def _no_shapes(pos2, ncol):
         return None
 
 
-def _too_many(e, sub):
-    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
-    if nbins > MAX_BINS:
-        return ValueError('%d bins: at most %d (PMX_PAIRS_ALIGN_MAX_BINS)' % (nbins, MAX_BINS))
-    return None
-
-
 def alignment_counts(pm, pos1, shape1, edges, pos2=None, shape2=None, weight1=None, weight2=None):
     """The position-shape and shape-shape sums of the rows in bins of r by the rule of the module docstring (mode 128):
     an AlignmentCounts.
@@ -162,7 +155,7 @@ def alignment_counts(pm, pos1, shape1, edges, pos2=None, shape2=None, weight1=No
     else:
         e, _, error = _binning(nd, edges, '1d', None, None, None, None, 2)
     if error is None:
-        error = _too_many(e, None)
+        error = too_many(e, None, MAX_BINS, '(PMX_PAIRS_ALIGN_MAX_BINS)')
     if error is None:
         b = float(e[-1])
         e2 = e * e
@@ -199,7 +192,7 @@ def projected_alignment_counts(pm, pos1, ellip1, edges, pos2=None, ellip2=None, 
     b = e2 = None
     e, sub, error = _binning(nd, edges, 'projected', None, None, piedges, pimax, los)
     if error is None:
-        error = _too_many(e, sub)
+        error = too_many(e, sub, MAX_BINS, '(PMX_PAIRS_ALIGN_MAX_BINS)')
     if error is None:
         b = float(max(e[-1], sub[-1]))
         e2 = e * e

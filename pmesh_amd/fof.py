@@ -25,19 +25,17 @@ The rule (normative; include/pmesh_amd.h restates it next to the entry points).
     cat = fof_catalog(pm, pos, res, mass=None, vel=vel)
     cat.Length, cat.Mass, cat.CMPosition, cat.CMVelocity
 
-On several ranks (nbodykit's merge loop): ``pm.decompose`` with a ghost width of b delivers every row to the ranks
-whose block it lies within b of; every rank groups its own rows and ghosts; then the labels are gathered back to the
-owners with a minimum over the copies (``Layout.gather(mode='min')``), exchanged out again and minimised over the
-local components, until no label changes on any rank.  Labels only decrease, so this ends.
+On several ranks (nbodykit's merge loop): the ghost layout of DESIGN.md §5.7.0 (``_cells.ghost_layout``) delivers every
+row to the ranks whose block it lies within b of; every rank groups its own rows and ghosts; then the labels are
+gathered back to the owners with a minimum over the copies (``Layout.gather(mode='min')``), exchanged out again and
+minimised over the local components, until no label changes on any rank.  Labels only decrease, so this ends.
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from ._arrays import to_device
-
-MAX_ROWS = _abi.PMX_FOF_MAX_ROWS
-CELLS_PER_ROW = _abi.PMX_FOF_CELLS_PER_ROW
+from ._cells import (allsum, block, box_of, cell_grid, cell_sort, ghost_layout, row_limit, rows, together,
+                     within_reach)
 
 
 class FOFResult(object):
@@ -60,80 +58,6 @@ class FOFCatalog(object):
         self.Length, self.Mass, self.CMPosition, self.CMVelocity = Length, Mass, CMPosition, CMVelocity
 
 
-def _together(comm, error):
-    """raise `error` (None, or an exception) on every rank when any rank has one"""
-    code = 0 if error is None else (1 if isinstance(error, TypeError) else 2)
-    worst = int(comm.allreduce(code, op='max')) if comm.size > 1 else code
-    if error is not None:
-        raise error
-    if worst:
-        raise (TypeError if worst == 1 else ValueError)('another rank refused its arguments')
-
-
-def _rows(pm, be, pos, what='pos', ncol=None, n=None):
-    """(tensor or None, error or None): `pos` as an (n, ncol) float tensor on the device"""
-    ncol = len(pm.Nmesh) if ncol is None else ncol
-    try:
-        t, _ = to_device(pos, be.device, what)
-    except TypeError as e:
-        return None, e
-    if ncol == 1 and t.dim() == 1:
-        t = t.reshape(-1, 1)
-    if t.dim() != 2 or t.shape[1] != ncol:
-        return None, ValueError('%s must have the shape (n, %d), not %s' % (what, ncol, tuple(t.shape)))
-    if n is not None and t.shape[0] != n:
-        return None, ValueError('%s must have %d rows, not %d' % (what, n, t.shape[0]))
-    return t, None
-
-
-def cell_grid(n, b, box, lo=None, hi=None):
-    """The cell grid of `n` rows for the linking length `b`: (ncell, origin, inv_side, periodic mask), per axis.
-
-    Without a block (one rank) every axis is periodic: origin 0, extent L_d.  With the block [lo, hi) of a rank, an axis
-    where the block plus 2 b covers the box is periodic as well; otherwise it is open, from lo_d - b over hi_d - lo_d +
-    2 b.  The cells have a side >= b on every axis, and there are at most max(1, PMX_FOF_CELLS_PER_ROW * n) of them:
-    the side grows to about the mean separation when b is smaller."""
-    nd = len(box)
-    box = numpy.asarray(box, dtype='f8')
-    origin, extent, mask = numpy.zeros(nd), box.copy(), 0
-    for d in range(nd):
-        if lo is not None and (hi[d] - lo[d]) + 2 * b < box[d]:
-            origin[d] = (lo[d] - b) % box[d]
-            extent[d] = (hi[d] - lo[d]) + 2 * b
-        else:
-            mask |= _abi.PMX_FOF_PERIODIC_X << d
-    most = numpy.maximum(numpy.floor(extent / b), 1)
-    most = numpy.where((extent / most < b) & (most > 1), most - 1, most)
-    cap = min(max(1, CELLS_PER_ROW * int(n)), MAX_ROWS)
-    ncell = most.copy()
-    side = (numpy.prod(extent) / cap) ** (1.0 / nd)
-    while numpy.prod(ncell) > cap:
-        ncell = numpy.clip(numpy.floor(extent / side), 1, most)
-        side *= 1.05
-    ncell = [int(c) for c in ncell]
-    return ncell, [float(o) for o in origin], [c / float(e) for c, e in zip(ncell, extent)], mask
-
-
-def cell_sort(be, pos, grid, box):
-    """pass 1 on the (n, ndim) rows: (wpos, cell_of, cell_start, order, spos, rows that are not finite)"""
-    ncell, origin, inv_side, mask = grid
-    n, nd = pos.shape
-    dev = pos.device
-    ncells = int(numpy.prod(ncell))
-    wpos = torch.empty((n, nd), dtype=torch.float64, device=dev)
-    spos = torch.empty((n, nd), dtype=torch.float64, device=dev)
-    cell_of = torch.empty(n, dtype=torch.int32, device=dev)
-    order = torch.empty(n, dtype=torch.int32, device=dev)
-    counts = torch.zeros(ncells, dtype=torch.int32, device=dev)
-    flagged = torch.zeros(1, dtype=torch.int64, device=dev)
-    be.fof_cells(pos, box, origin, inv_side, ncell, mask, wpos, cell_of, counts, flagged)
-    cell_start = torch.zeros(ncells + 1, dtype=torch.int32, device=dev)
-    cell_start[1:] = torch.cumsum(counts, 0)
-    counts.zero_()
-    be.fof_fill(wpos, cell_of, cell_start, counts, order, spos)
-    return wpos, cell_of, cell_start, order, spos, flagged
-
-
 def local_groups(be, pos, b, box, grid):
     """passes 1 to 3 on the rows of one rank: (root of every row: int32, rows that are not finite: device int64)"""
     wpos, cell_of, cell_start, order, spos, flagged = cell_sort(be, pos, grid, box)
@@ -142,15 +66,6 @@ def local_groups(be, pos, b, box, grid):
     be.fof_link(spos, order, cell_of, cell_start, grid[0], grid[3], box, b * b, parent)
     be.fof_flatten(parent)
     return parent, flagged
-
-
-def _block(pm):
-    """the low and high corners of this rank's real-field block in box units, or (None, None): one periodic grid"""
-    region = pm.domain.primary_region
-    if pm.comm.size == 1 or region is None or len(region['start']) != 1:
-        return None, None
-    h = numpy.asarray(pm.BoxSize, dtype='f8') / numpy.asarray(pm.Nmesh, dtype='f8')
-    return region['start'][0] * h, region['end'][0] * h
 
 
 def fof(pm, pos, linking_length, nmin=20, absolute=True):
@@ -162,44 +77,41 @@ def fof(pm, pos, linking_length, nmin=20, absolute=True):
         as in nbodykit.
     nmin : groups of fewer rows get the label 0.
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: parents are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them: parents are
+    32-bit.
     """
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
     if nd > _abi.PMX_MAXDIM:
         raise NotImplementedError('friends-of-friends on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
-    pos, error = _rows(pm, be, pos)
+    box = box_of(pm)
+    pos, error = rows(pm, be, pos)
     if error is None and not (int(nmin) == nmin and nmin >= 1):
         error = ValueError('nmin must be a positive integer')
-    _together(comm, error)
+    together(comm, error)
     n = pos.shape[0]
     sizes = [int(s) for s in comm.allgather(n)] if comm.size > 1 else [n]
     csize, offset = sum(sizes), sum(sizes[:comm.rank])
     b = float(linking_length)
     if not absolute and csize > 0:
         b *= (float(numpy.prod(box)) / csize) ** (1.0 / nd)
-    if not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+    if not within_reach(b, box):
         raise ValueError('the linking length must be finite, positive and at most half the shortest box side: %r' % b)
     dev = be.device
     gid = torch.arange(offset, offset + n, dtype=torch.int64, device=dev)
     iterations = 0
     if comm.size == 1:
-        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if n > MAX_ROWS else None)
+        row_limit(comm, n, ghosts=False)
         root, flagged = local_groups(be, pos, b, box, cell_grid(n, b, box))
         minid = gid
         be.fof_minlabel(root, minid, torch.empty_like(minid), torch.zeros(1, dtype=torch.int64, device=dev))
         nbad = int(flagged.cpu()[0])
     else:
-        # (a hair more than b: a pair at exactly b across a block face must not depend on the rounding of the routing)
-        smoothing = b * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-        layout = pm.decompose(pos, smoothing=smoothing)
-        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank')
-                  if layout.recvlength > MAX_ROWS else None)
+        layout = ghost_layout(pm, pos, b)
+        row_limit(comm, layout.recvlength, ghosts=True)
         rpos, val = layout.exchange(pos, gid)
-        lo, hi = _block(pm)
+        lo, hi = block(pm)
         root, flagged = local_groups(be, rpos, b, box, cell_grid(rpos.shape[0], b, box, lo, hi))
         work = torch.empty_like(val)
         changed = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -255,10 +167,6 @@ def _wrapped(x, box):
     return torch.where(w < box, w, torch.zeros_like(w))
 
 
-def _allsum(comm, t):
-    return t if comm.size == 1 else comm.allreduce(t)
-
-
 def fof_catalog(pm, pos, result, mass=None, vel=None):
     """The halo catalogue of the FOFResult `result` of the same `pos`: an FOFCatalog.
 
@@ -281,12 +189,12 @@ def fof_catalog(pm, pos, result, mass=None, vel=None):
     for what, x, ncol in (('pos', pos, nd), ('mass', mass, 1), ('vel', vel, nd)):
         t = None
         if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, ncol, n)
+            t, error = rows(pm, be, x, what, ncol, n)
         cols.append(t)
-    _together(comm, error)
+    together(comm, error)
     pos, mass, vel = cols
     dev = be.device
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     boxt = torch.tensor(box, dtype=torch.float64, device=dev)
     ng = result.ngroups
     # the reference member of every group: the row whose global index is the group's minid, on the rank that owns it
@@ -294,10 +202,10 @@ def fof_catalog(pm, pos, result, mass=None, vel=None):
     gid = torch.arange(result.offset, result.offset + n, dtype=torch.int64, device=dev)
     sel = torch.nonzero((result.labels > 0) & (gid == result.minid)).reshape(-1)
     ref[result.labels[sel]] = pos[sel].to(torch.float64)
-    ref = _allsum(comm, ref)
+    ref = allsum(comm, ref)
     out = torch.zeros((ng + 1, 1 + 2 * nd), dtype=torch.float64, device=dev)
     be.fof_group_sums(pos, result.labels, mass, vel, ref, box, out)
-    out = _allsum(comm, out)
+    out = allsum(comm, out)
     total = out[:, 0:1].clone()
     total[0] = 1.0
     cm = _wrapped(_wrapped(ref, boxt) + out[:, 1:1 + nd] / total, boxt)

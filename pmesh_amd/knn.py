@@ -28,8 +28,8 @@ The rule (normative; include/pmesh_amd.h restates it next to the entry point).
    The row itself has ``r2 == 0`` exactly, so the values are those of "every other row, coincident ones included at
    r2 = 0".  Identity is the global index, not the position.
 5. Limits.  ``1 <= k <= PMX_KNN_MAX_K`` (64) in the cross form, ``k <= 63`` in the auto form.  Rows that are not finite
-   raise ValueError with their number; more than 2^31 - 1 rows on one rank, ghosts included, raise ValueError.  Every
-   argument error is raised on all ranks together.
+   raise ValueError with their number, and so does a rank past the row limit of DESIGN.md §5.7.0.  Every argument
+   error is raised on all ranks together.
 
     from pmesh_amd.knn import knn, knn_density, knn_cdf
     res = knn(pm, pos, 32)                        # res.dist2, res.dist, res.index, res.found, res.rounds
@@ -44,16 +44,16 @@ are not searched again; the others go to the next round on a new grid; the round
 its rows keep what they have, inf-padded.  One host synchronisation per round counts the unresolved rows (with ranks,
 one allreduce).  By rule 3 the result depends neither on ``R_0`` nor on the schedule.
 
-On several ranks, per round, the routing is that of pair_counts: the unresolved primaries go to their owners
-(``pm.decompose`` without ghosts), the sources to every rank whose block they lie within ``R_t`` of, and an int64 column
-of their global indices travels with them; the kernel's local indices are mapped through that column on the device, and
-``Layout.gather`` returns the rows to their callers (every primary has one owner).
+Host, per round: the routing of DESIGN.md §5.7.0 (``_cells.Neighbourhood``) of the unresolved primaries and all sources
+with the radius ``R_t``.  On several ranks an int64 column of the sources' global indices travels with them; the
+kernel's local indices are mapped through that column on the device, and the rows return to their callers with the mode
+'min' (every primary has one owner).
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from .fof import MAX_ROWS, _block, _rows, _together, cell_grid, cell_sort
+from ._cells import Neighbourhood, box_of, read_rows, refuse_not_finite, rows, sorted_sets, together, within_reach
 
 MAX_K = _abi.PMX_KNN_MAX_K
 
@@ -95,20 +95,16 @@ def first_radius(n2_total, k, box):
 
 
 def local_knn(be, pos1, pos2, grid, box, r2max, k, index=True):
-    """One launch on the rows of one rank on the cell grid `grid` (of fof.cell_grid, its cells of a side >= the radius):
-    the k smallest r2 < r2max of every row of `pos1` among the rows of `pos2` (None: pos1 itself, the row included).
-    Returns (dist2 (n1, k) float64, index (n1, k) int32 local rows of pos2 or None, count (n1,) int64: the sources with
-    r2 < r2max, not capped) in the row order of pos1."""
+    """One launch on the rows of one rank on the cell grid `grid` (of _cells.cell_grid, its cells of a side >= the
+    radius): the k smallest r2 < r2max of every row of `pos1` among the rows of `pos2` (None: pos1 itself, the row
+    included).  Returns (dist2 (n1, k) float64, index (n1, k) int32 local rows of pos2 or None, count (n1,) int64: the
+    sources with r2 < r2max, not capped) in the row order of pos1."""
     dev = pos1.device
     n1 = pos1.shape[0]
     dist2 = torch.empty((n1, k), dtype=torch.float64, device=dev)
     idx = torch.empty((n1, k), dtype=torch.int32, device=dev) if index else None
     count = torch.empty(n1, dtype=torch.int64, device=dev)
-    _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
-    if pos2 is None:
-        order2, cell_start2, spos2 = order1, cell_start1, spos1
-    else:
-        _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
+    spos1, order1, cell_of1, spos2, order2, cell_start2 = sorted_sets(be, pos1, pos2, grid, box)
     be.knn(spos1, order1, cell_of1, spos2, order2, cell_start2, grid[0], grid[3], box, r2max, k, dist2, idx, count)
     return dist2, idx, count
 
@@ -120,7 +116,7 @@ def _count(comm, n):
 def _arguments(pm, be, pos, pos2, k, rmax):
     """(box, pos, pos2, k, rmax, error) of knn()"""
     nd = len(pm.Nmesh)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     error = None
     auto = pos2 is None
     try:
@@ -139,15 +135,10 @@ def _arguments(pm, be, pos, pos2, k, rmax):
             rm = min(box) / 2 if rmax is None else float(rmax)
         except (TypeError, ValueError):
             rm = numpy.nan
-        if not (numpy.isfinite(rm) and rm > 0 and 2 * rm <= min(box)):
+        if not within_reach(rm, box):
             error = ValueError('rmax must be finite, positive and at most half the shortest box side: %r' % (rmax,))
-    rows = []
-    for what, x in (('pos', pos), ('pos2', pos2)):
-        t = None
-        if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, nd)
-        rows.append(t)
-    return box, rows[0], rows[1], kk, rm, error
+    (pos, pos2), error = read_rows(pm, be, (('pos', pos, nd, None), ('pos2', pos2, nd, None)), error)
+    return box, pos, pos2, kk, rm, error
 
 
 def knn(pm, pos, k, pos2=None, rmax=None, index=True):
@@ -160,8 +151,7 @@ def knn(pm, pos, k, pos2=None, rmax=None, index=True):
     rmax : sources at rmax and beyond are no neighbours; the default is half the shortest box side.
     index : False leaves ``index`` None (the auto form still forms it: identity is the index).
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them.
     """
     be = backend.get()
     comm = pm.comm
@@ -169,13 +159,10 @@ def knn(pm, pos, k, pos2=None, rmax=None, index=True):
     if nd > _abi.PMX_MAXDIM:
         raise NotImplementedError('nearest neighbours on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
     box, pos, pos2, k, rmax, error = _arguments(pm, be, pos, pos2, k, rmax)
-    _together(comm, error)
+    together(comm, error)
     auto = pos2 is None
     src = pos if auto else pos2
-    nbad = int((~torch.isfinite(pos)).any(dim=1).sum()) + (0 if auto else int((~torch.isfinite(src)).any(dim=1).sum()))
-    nbad = _count(comm, nbad)
-    if nbad:
-        raise ValueError('%d rows of pos and pos2 have a coordinate that is not finite' % nbad)
+    refuse_not_finite(comm, 'pos and pos2', pos, pos2)
     dev = be.device
     n1, n2 = pos.shape[0], src.shape[0]
     kk = k + 1 if auto else k
@@ -197,33 +184,17 @@ def knn(pm, pos, k, pos2=None, rmax=None, index=True):
         last = not radius < rmax
         radius, r2 = (rmax, rmax2) if last else (radius, radius * radius)
         p1 = pos if todo is None else pos[todo]
-        if comm.size == 1:
-            most = max(p1.shape[0], n2)
-            _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-            d, ix, cnt = local_knn(be, p1, None if auto and todo is None else src, cell_grid(most, radius, box), box,
-                                   r2, kk, want_index)
-            if want_index:
-                ix = ix.to(torch.int64)
-        else:
-            # the routing of pair_counts: the primaries to their owners, the sources to every rank whose block they
-            # lie within the radius of (a hair more: a pair just inside it across a block face must not depend on the
-            # rounding of the routing)
-            own = pm.decompose(p1, smoothing=0)
-            smoothing = radius * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-            ghosts = pm.decompose(src, smoothing=smoothing)
-            most = max(own.recvlength, ghosts.recvlength)
-            _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
-            q1 = own.exchange(p1)
-            q2, g2 = ghosts.exchange(src, gid2)
-            lo, hi = _block(pm)
-            d, ix, cnt = local_knn(be, q1, q2, cell_grid(most, radius, box, lo, hi), box, r2, kk, want_index)
-            # every primary has exactly one owner: the minimum over its copies is its value
-            d = own.gather(d, mode='min')
-            cnt = own.gather(cnt, mode='min')
-            if want_index:
-                ix = ix.to(torch.int64)
+        hood = Neighbourhood(pm, radius, p1, None if auto and todo is None else src)
+        q1 = hood.to_owners(p1)
+        q2, g2 = hood.to_sources(src, gid2)
+        d, ix, cnt = local_knn(be, q1, None if hood.same else q2, hood.grid, box, r2, kk, want_index)
+        d, cnt = hood.to_callers(d, 'min'), hood.to_callers(cnt, 'min')
+        if want_index:
+            ix = ix.to(torch.int64)
+            if comm.size > 1:
+                # the kernel's rows of q2 are not the sources' global rows
                 ix = torch.where(ix >= 0, g2[ix.clamp(min=0)] if g2.numel() else ix, torch.full_like(ix, -1))
-                ix = own.gather(ix, mode='min')
+            ix = hood.to_callers(ix, 'min')
         # (the rows that are not resolved are written again in a later round)
         if todo is None:
             dist2 = d
@@ -277,10 +248,10 @@ def knn_density(pm, pos, k=32, pos2=None, mass2=None, rmax=None):
         raise NotImplementedError('nearest neighbours on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
     error = m = None
     if mass2 is not None:
-        src, error = _rows(pm, be, pos if pos2 is None else pos2, 'pos' if pos2 is None else 'pos2', nd)
+        src, error = rows(pm, be, pos if pos2 is None else pos2, 'pos' if pos2 is None else 'pos2', nd)
         if error is None:
-            m, error = _rows(pm, be, mass2, 'mass2', 1, src.shape[0])
-    _together(comm, error)
+            m, error = rows(pm, be, mass2, 'mass2', 1, src.shape[0])
+    together(comm, error)
     res = knn(pm, pos, k, pos2=pos2, rmax=rmax, index=mass2 is not None)
     if m is None:
         total = float(res.k)
@@ -320,7 +291,7 @@ def knn_cdf(pm, data, query, ks, redges, rmax=None):
         error = ValueError('redges must be finite, not negative and not decreasing, the last one positive')
     if error is None and rmax is not None and not float(rmax) >= e[-1]:
         error = ValueError('rmax must be at least redges[-1]')
-    _together(comm, error)
+    together(comm, error)
     res = knn(pm, query, max(kl), pos2=data, rmax=float(e[-1]) if rmax is None else rmax, index=False)
     e2 = torch.from_numpy(e * e).to(res.dist2.device)
     cols = res.dist2[:, torch.tensor([a - 1 for a in kl], dtype=torch.int64, device=res.dist2.device)]

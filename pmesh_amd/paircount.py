@@ -38,18 +38,16 @@ The rule (normative; include/pmesh_amd.h restates it next to the entry point).
     pc.npairs, pc.wnpairs, pc.rsum, pc.rmean
     xi, pc = pair_correlation(pm, pos, edges, mode='2d', Nmu=100)  # xi(r, mu), natural estimator, analytic randoms
 
-On one rank both sets are sorted into one periodic cell grid of side >= b (``fof.cell_grid`` / ``fof.cell_sort``) and
-one kernel counts.  On several ranks the primaries go to their owners (``pm.decompose`` without ghosts), the
-secondaries to every rank whose block they lie within b of; each rank counts its primaries against its secondaries,
-and one allreduce sums the three arrays: every ordered pair is counted on exactly one rank.  In the auto form the self
-pairs are subtracted on the host: they have r2 == 0 exactly, so they sit in bin (0, 0) when edges[0] == 0 and nowhere
+Host: the routing of DESIGN.md §5.7.0 (``_cells.Neighbourhood``) with the radius b; each rank counts its primaries
+against its secondaries with one kernel, and one allreduce per array sums the three.  In the auto form the self pairs
+are subtracted on the host: they have r2 == 0 exactly, so they sit in bin (0, 0) when edges[0] == 0 and nowhere
 otherwise.
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from .fof import MAX_ROWS, _allsum, _block, _rows, _together, cell_grid, cell_sort
+from ._cells import Neighbourhood, allsum, box_of, read_rows, refuse_not_finite, sorted_sets, together, within_reach
 
 MAX_BINS = _abi.PMX_PAIRS_MAX_BINS
 MODES = {'1d': _abi.PMX_PAIRS_1D, '2d': _abi.PMX_PAIRS_2D, 'projected': _abi.PMX_PAIRS_PROJECTED}
@@ -154,6 +152,15 @@ def _edges(x, what, first=None, last=None):
     return e, None
 
 
+def too_many(e, sub, limit, what):
+    """None, or the error of more than `limit` bins of the edges `e` and the sub edges `sub` (None: one sub bin); `what`
+    ends the message: the name of the limit"""
+    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
+    if nbins > limit:
+        return ValueError('%d bins: at most %d %s' % (nbins, limit, what))
+    return None
+
+
 def _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los):
     """(edges, sub edges or None, error) of the arguments that say how to bin"""
     if mode not in MODES:
@@ -181,14 +188,12 @@ def _binning(nd, edges, mode, muedges, Nmu, piedges, pimax, los):
             sub, error = _edges(piedges, 'piedges', first=0.0)
         if error is not None:
             return None, None, error
-    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
-    if nbins > MAX_BINS:
-        return None, None, ValueError('%d bins: at most %d (PMX_PAIRS_MAX_BINS)' % (nbins, MAX_BINS))
-    return e, sub, None
+    error = too_many(e, sub, MAX_BINS, '(PMX_PAIRS_MAX_BINS)')
+    return (e, sub, None) if error is None else (None, None, error)
 
 
 def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub):
-    """The three arrays of the rows of one rank on the cell grid `grid` (of fof.cell_grid): every row of `pos1` with
+    """The three arrays of the rows of one rank on the cell grid `grid` (of _cells.cell_grid): every row of `pos1` with
     every row of `pos2` (None: with every row of pos1, itself included: the caller subtracts the self pairs).  e2 and
     sub: device tensors.  mode: a key of KERNEL_MODES.  Returns (npairs, wnpairs, rsum), flat.  In the modes of
     VELOCITY_MODES weight1 and weight2 are the (n, ncol) blocks of columns of the two sets and rsum has 4 * nbins
@@ -207,11 +212,9 @@ def local_counts(be, mode, los, pos1, weight1, pos2, weight2, grid, box, e2, sub
     npairs = torch.zeros(ncount, dtype=torch.int64, device=dev)
     wnpairs = torch.zeros(ncount, dtype=torch.float64, device=dev)
     rsum = torch.zeros(nrsum, dtype=torch.float64, device=dev)
-    _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
+    spos1, order1, cell_of1, spos2, order2, cell_start2 = sorted_sets(be, pos1, pos2, grid, box)
     if pos2 is None:
-        order2, cell_start2, spos2, weight2 = order1, cell_start1, spos1, weight1
-    else:
-        _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
+        weight2 = weight1
     be.pair_counts(KERNEL_MODES[mode], los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2,
                    grid[0], grid[3], box, e2, sub, npairs, wnpairs, rsum)
     return npairs, wnpairs, rsum
@@ -224,7 +227,7 @@ def _weight_sums(comm, w, n):
         return total, total
     w = w.to(torch.float64)
     s = torch.stack([w.sum(), (w * w).sum()])
-    s = _allsum(comm, s).cpu()
+    s = allsum(comm, s).cpu()
     return float(s[0]), float(s[1])
 
 
@@ -239,7 +242,7 @@ def _block_of(weight, cols):
 def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, prepare=None, columns=None,
            self_pairs=True):
     """What the public counting calls share behind their own reading of the binning: the argument checks of the rows
-    and the weights, the weight sums, the routing on one rank or several, the allreduce and the self pairs.
+    and the weights, the weight sums, the routing, the allreduce and the self pairs.
 
     kernel : the mode of local_counts.  e2, sub : float64 numpy arrays, what the kernel is given (sub None in 1d).
     b : the search radius, or None with `error`.  error : what the caller found wrong already, or None.
@@ -259,9 +262,9 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     auto = pos2 is None
-    if error is None and not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+    if error is None and not within_reach(b, box):
         error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
                            'side: %r' % b)
     if error is None and auto and weight2 is not None:
@@ -274,29 +277,16 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
         if error is None and (x2 is None) != auto:
             error = ValueError('%s2 needs pos2' % name if auto else 'pos2 needs %s2' % name)
         wanted += [(name + '1', x1, ncol, 0), (name + '2', x2, ncol, 1)]
-    rows = []
-    for what, x, ncol, of in wanted:
-        t = None
-        if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
-        rows.append(t)
-    _together(comm, error)
+    rows, error = read_rows(pm, be, wanted, error)
+    together(comm, error)
     pos1, pos2, weight1, weight2 = rows[:4]
     if weight1 is not None:
         weight1 = weight1.reshape(-1)
     if weight2 is not None:
         weight2 = weight2.reshape(-1)
-    nbad = int((~torch.isfinite(pos1)).any(dim=1).sum()) + (0 if auto else int((~torch.isfinite(pos2)).any(dim=1).sum()))
-    if comm.size > 1:
-        nbad = int(comm.allreduce(nbad))
-    if nbad:
-        raise ValueError('%d rows of pos1 and pos2 have a coordinate that is not finite' % nbad)
+    refuse_not_finite(comm, 'pos1 and pos2', pos1, pos2)
     if columns is not None:
-        nbad = sum(int((~torch.isfinite(x)).any(dim=1).sum()) for x in rows[4:] if x is not None)
-        if comm.size > 1:
-            nbad = int(comm.allreduce(nbad))
-        if nbad:
-            raise ValueError('%d rows of %s1 and %s2 have an entry that is not finite' % (nbad, columns[0], columns[0]))
+        refuse_not_finite(comm, '%s1 and %s2' % (columns[0], columns[0]), *rows[4:], entry='an entry')
         if len(columns) > 4:
             nbad = sum(int((x == 0).all(dim=1).sum()) for x, on in zip(rows[4:], columns[4]) if x is not None and on)
             if comm.size > 1:
@@ -317,30 +307,11 @@ def _count(pm, pos1, pos2, weight1, weight2, kernel, los, e2, sub, b, error, pre
     first = e2[0]
     e2 = torch.from_numpy(numpy.ascontiguousarray(e2, dtype='f8')).to(dev)
     subt = None if sub is None else torch.from_numpy(numpy.ascontiguousarray(sub, dtype='f8')).to(dev)
-    if comm.size == 1:
-        most = max(n1, 0 if auto else pos2.shape[0])
-        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-        sums = local_counts(be, kernel, los, pos1, weight1, pos2, weight2, cell_grid(most, b, box), box, e2, subt)
-    else:
-        # the primaries to their owners; the secondaries to every rank whose block they lie within b of (a hair more
-        # than b: a pair at exactly b across a block face must not depend on the rounding of the routing)
-        own = pm.decompose(pos1, smoothing=0)
-        smoothing = b * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-        ghosts = pm.decompose(pos1 if auto else pos2, smoothing=smoothing)
-        most = max(own.recvlength, ghosts.recvlength)
-        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
-        p1 = own.exchange(pos1)
-        # (a layout remembers its last exchange by the address and shape of the tensor: the rows of a rank that holds
-        # none and its block of as many columns, as in the mode projected-align, share both)
-        own.forget()
-        q1 = own.exchange(weight1) if weight1 is not None else None
-        p2 = ghosts.exchange(pos1 if auto else pos2)
-        ghosts.forget()
-        w2 = weight1 if auto else weight2
-        q2 = ghosts.exchange(w2) if w2 is not None else None
-        lo, hi = _block(pm)
-        sums = local_counts(be, kernel, los, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
-        sums = [_allsum(comm, s) for s in sums]
+    hood = Neighbourhood(pm, b, pos1, pos2)
+    p1, q1 = hood.to_owners(pos1), hood.to_owners(weight1)
+    p2, q2 = hood.to_sources(pos1 if auto else pos2), hood.to_sources(weight1 if auto else weight2)
+    sums = local_counts(be, kernel, los, p1, q1, None if hood.same else p2, q2, hood.grid, box, e2, subt)
+    sums = [hood.allsum(x) for x in sums]
     npairs, wnpairs, rsum = sums
     if self_pairs and auto and first == 0:
         # the self pairs: r2 == 0 exactly, bin (0, 0)
@@ -361,8 +332,7 @@ def pair_counts(pm, pos1, edges, pos2=None, weight1=None, weight2=None, mode='1d
     mode : '1d', '2d' or 'projected'.  muedges, or Nmu for Nmu uniform bins of mu in [0, 1]; piedges, or pimax for bins
         of unit width in [0, pimax]: nbodykit's conventions.  los : the axis of the line of sight.
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them.
     """
     nd = len(pm.Nmesh)
     if nd > _abi.PMX_MAXDIM:

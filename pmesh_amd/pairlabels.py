@@ -54,8 +54,8 @@ import torch
 
 from . import _abi, backend
 from ._arrays import to_device
-from .fof import _allsum, _rows, _together
-from .paircount import LABEL_SLOTS, PairCounts, _binning, _count, bin_volumes, label_slots
+from ._cells import allsum, box_of, rows, together
+from .paircount import LABEL_SLOTS, PairCounts, _binning, _count, bin_volumes, label_slots, too_many
 from .surveypairs import KERNELS as SURVEY_KERNELS
 from .surveypairs import SurveyPairCounts, _observer, _preparation, _survey_binning
 
@@ -145,7 +145,7 @@ def box_regions(pm, pos, nsub):
     finite gets -1."""
     be = backend.get()
     nd = len(pm.Nmesh)
-    pos, error = _rows(pm, be, pos)
+    pos, error = rows(pm, be, pos)
     ns = None
     if error is None:
         try:
@@ -154,8 +154,8 @@ def box_regions(pm, pos, nsub):
             pass
         if ns is None or not ((ns == numpy.floor(ns)) & (ns >= 1)).all():
             error = ValueError('nsub must be positive integers, one or one per axis')
-    _together(pm.comm, error)
-    box = numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))
+    together(pm.comm, error)
+    box = numpy.asarray(box_of(pm))
     x = pos.to(torch.float64)
     label = torch.zeros(x.shape[0], dtype=torch.int64, device=x.device)
     for d in range(nd):
@@ -207,7 +207,7 @@ def _read(pm, pos1, label1, pos2, label2, nlab, error):
             error = ValueError('labels must lie in [0, %s), or be negative for a row that is in nothing: found %d'
                                % ('2^53' if nlab is None else '%d' % nlab, top))
     # every rank learns of an error of any rank here, and of the largest label
-    _together(comm, error)
+    together(comm, error)
     if comm.size > 1:
         top = int(comm.allreduce(top, op='max'))
     return l1, l2, (torch.float32 if top <= EXACT32 else torch.float64), None
@@ -227,7 +227,7 @@ def _weights(pm, weight, n, dev):
     """the weights of one set as an (n,) float64 device tensor (after _count has accepted them)"""
     if weight is None:
         return torch.ones(n, dtype=torch.float64, device=dev)
-    t, _ = _rows(pm, backend.get(), weight, 'weight', 1, n)
+    t, _ = rows(pm, backend.get(), weight, 'weight', 1, n)
     return t.reshape(-1).to(torch.float64)
 
 
@@ -240,15 +240,8 @@ def _per_label(comm, label, w, nlab):
     out[0].index_add_(0, lab, torch.ones_like(w))
     out[1].index_add_(0, lab, w)
     out[2].index_add_(0, lab, w * w)
-    out = _allsum(comm, out).cpu().numpy()
+    out = allsum(comm, out).cpu().numpy()
     return out[0], out[1], out[2]
-
-
-def _too_many(e, sub):
-    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
-    if nbins > MAX_BINS:
-        return ValueError('%d bins: at most %d in the modes by row labels (PMX_PAIRS_LABEL_SLOTS / 4)' % (nbins, MAX_BINS))
-    return None
 
 
 class _Binning(object):
@@ -261,7 +254,7 @@ class _Binning(object):
         if nd > _abi.PMX_MAXDIM:
             raise NotImplementedError('pair counts on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
         self.pm, self.mode, self.survey, self.nd = pm, mode, survey, nd
-        self.box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+        self.box = box_of(pm)
         self.prepare = self.R = self.obs = self.thetaedges = None
         self.e = self.sub = self.e2 = self.given = self.b = None
         if survey:
@@ -283,7 +276,7 @@ class _Binning(object):
                 self.e2 = self.e * self.e
                 self.given = self.sub * self.sub if mode == '2d' else self.sub
         if self.error is None:
-            self.error = _too_many(self.e, self.sub)
+            self.error = too_many(self.e, self.sub, MAX_BINS, 'in the modes by row labels (PMX_PAIRS_LABEL_SLOTS / 4)')
         if self.error is None:
             self.shape = (len(self.e) - 1,) if self.sub is None else (len(self.e) - 1, len(self.sub) - 1)
             self.nbins = int(numpy.prod(self.shape))
@@ -340,7 +333,7 @@ def _split(bn, pos1, label1, pos2, label2, weight1, weight2):
         w = _weights(pm, weight1, l1.shape[0], l1.device)
         has = l1 >= 0
         s = torch.stack([has.sum().to(torch.float64), (~has).sum().to(torch.float64), (w * w)[has].sum()])
-        s = _allsum(pm.comm, s).cpu().numpy()
+        s = allsum(pm.comm, s).cpu().numpy()
         npairs[nb] -= int(s[0])
         wnpairs[nb] -= float(s[2])
         npairs[0] -= int(s[1])

@@ -56,11 +56,11 @@ raise ValueError.  The search radius, the finiteness of the rows and the ranks a
     pv = pairwise_velocities(pm, pos, vel, edges, mode='projected', pimax=40)   # (rp, pi): pv.v12 is v_los(rp, pi)
     ks = pairwise_los(pm, pos, T, edges, observer=obs)             # ks.v12 = num / den; the kSZ momentum is -ks.v12
 """
-import numpy
 import torch
 
 from . import _abi
-from .paircount import PairCounts, _binning, _count
+from ._cells import box_of
+from .paircount import PairCounts, _binning, _count, too_many
 from .surveypairs import _observer, _preparation
 
 MAX_BINS = _abi.PMX_PAIRS_VELOCITY_MAX_BINS
@@ -105,13 +105,6 @@ class PairwiseLOS(PairCounts):
         self.v12 = _ratio(self.num, self.den, (npairs > 0) & (self.den != 0))
 
 
-def _too_many(e, sub):
-    nbins = (len(e) - 1) * (len(sub) - 1 if sub is not None else 1)
-    if nbins > MAX_BINS:
-        return ValueError('%d bins: at most %d (PMX_PAIRS_VELOCITY_MAX_BINS)' % (nbins, MAX_BINS))
-    return None
-
-
 def pairwise_velocities(pm, pos1, vel1, edges, pos2=None, vel2=None, weight1=None, weight2=None, mode='1d',
                         piedges=None, pimax=None, los=2):
     """The pairwise velocity sums of the rows by the rule of the module docstring: a PairwiseVelocities.
@@ -138,7 +131,7 @@ def pairwise_velocities(pm, pos1, vel1, edges, pos2=None, vel2=None, weight1=Non
     else:
         e, sub, error = _binning(nd, edges, mode, None, None, piedges, pimax, los)
     if error is None:
-        error = _too_many(e, sub)
+        error = too_many(e, sub, MAX_BINS, '(PMX_PAIRS_VELOCITY_MAX_BINS)')
     if error is None:
         b = float(max(e[-1], sub[-1])) if mode == 'projected' else float(e[-1])
         e2 = e * e
@@ -170,14 +163,14 @@ def pairwise_los(pm, pos1, s1, edges, observer=None, pos2=None, s2=None, weight1
     Argument errors and a row outside ``[b / 2, L_d - b / 2)`` raise on every rank together.
     """
     nd = len(pm.Nmesh)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     e = b = e2 = obs = None
     if nd != 3:
         error = ValueError('pairwise_los needs a mesh of three dimensions, not %d' % nd)
     else:
         e, _, error = _binning(nd, edges, '1d', None, None, None, None, 2)
     if error is None:
-        error = _too_many(e, None)
+        error = too_many(e, None, MAX_BINS, '(PMX_PAIRS_VELOCITY_MAX_BINS)')
     if error is None:
         obs, error = _observer(observer, box)
     if error is None:

@@ -31,17 +31,16 @@ The rule (normative; include/pmesh_amd.h restates it next to the entry point).
     prof.density(), prof.cumulative()                                  # rho(r) and M(< r) of every centre
     so = so_masses(pm, cat.CMPosition, pos, 200, rho_mean, mass=m)     # so.radius, so.mass, so.found
 
-On one rank both sets are sorted into one periodic cell grid of side >= b (``fof.cell_grid`` / ``fof.cell_sort``) and
-one kernel fills all histograms.  On several ranks the routing is that of ``knn``: the centres go to their owners
-(``pm.decompose`` without ghosts), the sources to every rank whose block they lie within b of, and ``Layout.gather``
-returns the histograms to the caller's rows.  Every centre has one owner: there is no allreduce.  With fewer centres
+Host: the routing of DESIGN.md §5.7.0 (``_cells.Neighbourhood``) with the centres as primaries and the radius b; one
+kernel per rank fills all histograms, and they return to the caller's rows with the mode 'min'.  Every centre has one
+owner: there is no allreduce.  With fewer centres
 than the device has wave slots (a few thousand) the device is under-filled; a row is not split over several waves.
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from .fof import MAX_ROWS, _block, _rows, _together, cell_grid, cell_sort
+from ._cells import Neighbourhood, box_of, read_rows, refuse_not_finite, sorted_sets, together, within_reach
 from .knn import ball_volume
 from .paircount import _binning, bin_volumes
 
@@ -100,7 +99,7 @@ class SOResult(object):
 
 
 def local_profiles(be, mode, los, centres, pos, weight1, weight2, grid, box, e2, sub):
-    """The histograms of the rows of one rank on the cell grid `grid` (of fof.cell_grid): every row of `centres` with
+    """The histograms of the rows of one rank on the cell grid `grid` (of _cells.cell_grid): every row of `centres` with
     every row of `pos`.  e2 and sub: device tensors.  mode: a key of ROW_MODES.  Returns (npairs, wnpairs, rsum) of the
     shape (n1, nr, nsub) in the row order of `centres`."""
     dev = centres.device
@@ -109,8 +108,7 @@ def local_profiles(be, mode, los, centres, pos, weight1, weight2, grid, box, e2,
     npairs = torch.zeros(shape, dtype=torch.int64, device=dev)
     wnpairs = torch.zeros(shape, dtype=torch.float64, device=dev)
     rsum = torch.zeros(shape, dtype=torch.float64, device=dev)
-    _, cell_of1, _, order1, spos1, _ = cell_sort(be, centres, grid, box)
-    _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos, grid, box)
+    spos1, order1, cell_of1, spos2, order2, cell_start2 = sorted_sets(be, centres, pos, grid, box)
     be.pair_counts(ROW_MODES[mode], los, spos1, order1, cell_of1, weight1, spos2, order2, cell_start2, weight2,
                    grid[0], grid[3], box, e2, sub, npairs, wnpairs, rsum)
     return npairs, wnpairs, rsum
@@ -128,15 +126,14 @@ def radial_profiles(pm, centres, pos, edges, mass=None, weight=None, mode='1d', 
     mode : '1d' or 'projected'.  piedges, or pimax for bins of unit width in [0, pimax]; los : the axis of the line of
         sight (the conventions of pair_counts).
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them.
     """
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
     if nd > _abi.PMX_MAXDIM:
         raise NotImplementedError('profiles on meshes of more than %d dimensions' % _abi.PMX_MAXDIM)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     e = sub = b = None
     if mode not in ROW_MODES:
         error = ValueError("mode must be '1d' or 'projected', not %r" % (mode,))
@@ -148,51 +145,26 @@ def radial_profiles(pm, centres, pos, edges, mass=None, weight=None, mode='1d', 
             error = ValueError('%d bins per centre: at most %d (PMX_PAIRS_ROWS_MAX_BINS)' % (nbins, MAX_BINS))
     if error is None:
         b = float(numpy.hypot(e[-1], sub[-1])) if mode == 'projected' else float(e[-1])
-        if not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+        if not within_reach(b, box):
             error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
                                'side: %r' % b)
-    rows = []
-    for what, x, ncol, of in (('centres', centres, nd, None), ('pos', pos, nd, None), ('weight', weight, 1, 0),
-                              ('mass', mass, 1, 1)):
-        t = None
-        if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
-        rows.append(t)
-    _together(comm, error)
-    centres, pos, weight, mass = rows
+    wanted = (('centres', centres, nd, None), ('pos', pos, nd, None), ('weight', weight, 1, 0), ('mass', mass, 1, 1))
+    (centres, pos, weight, mass), error = read_rows(pm, be, wanted, error)
+    together(comm, error)
     if weight is not None:
         weight = weight.reshape(-1)
     if mass is not None:
         mass = mass.reshape(-1)
-    nbad = int((~torch.isfinite(centres)).any(dim=1).sum()) + int((~torch.isfinite(pos)).any(dim=1).sum())
-    if comm.size > 1:
-        nbad = int(comm.allreduce(nbad))
-    if nbad:
-        raise ValueError('%d rows of centres and pos have a coordinate that is not finite' % nbad)
+    refuse_not_finite(comm, 'centres and pos', centres, pos)
     dev = be.device
     e2 = torch.from_numpy(numpy.ascontiguousarray(e * e)).to(dev)
     subt = None if sub is None else torch.from_numpy(numpy.ascontiguousarray(sub)).to(dev)
     nc = centres.shape[0]
-    if comm.size == 1:
-        most = max(nc, pos.shape[0])
-        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-        sums = local_profiles(be, mode, los, centres, pos, weight, mass, cell_grid(most, b, box), box, e2, subt)
-    else:
-        # the routing of knn: the centres to their owners, the sources to every rank whose block they lie within b of
-        # (a hair more than b: a pair at exactly b across a block face must not depend on the rounding of the routing)
-        own = pm.decompose(centres, smoothing=0)
-        smoothing = b * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-        ghosts = pm.decompose(pos, smoothing=smoothing)
-        most = max(own.recvlength, ghosts.recvlength)
-        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
-        p1 = own.exchange(centres)
-        q1 = own.exchange(weight) if weight is not None else None
-        p2 = ghosts.exchange(pos)
-        q2 = ghosts.exchange(mass) if mass is not None else None
-        lo, hi = _block(pm)
-        sums = local_profiles(be, mode, los, p1, p2, q1, q2, cell_grid(most, b, box, lo, hi), box, e2, subt)
-        # every centre has exactly one owner: the minimum over its copies is its value
-        sums = [own.gather(s.reshape(s.shape[0], -1), mode='min') for s in sums]
+    hood = Neighbourhood(pm, b, centres, pos)
+    p1, q1 = hood.to_owners(centres), hood.to_owners(weight)
+    p2, q2 = hood.to_sources(pos), hood.to_sources(mass)
+    sums = local_profiles(be, mode, los, p1, p2, q1, q2, hood.grid, box, e2, subt)
+    sums = [hood.to_callers(x.flatten(1), 'min') for x in sums]
     shape = (nc, len(e) - 1) if sub is None else (nc, len(e) - 1, len(sub) - 1)
     npart, wsum, rsum = [s.reshape(shape) for s in sums]
     return ProfileResult(npart, wsum, rsum, e, sub, mode, los, nd)
@@ -214,7 +186,7 @@ def so_masses(pm, centres, pos, delta, rho_ref, mass=None, rmin=None, rmax=None,
     on top of one radial_profiles call: there is no host loop over the centres.
     """
     nd = len(pm.Nmesh)
-    box = numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))
+    box = box_of(pm)
     error = edges = None
     try:
         delta, rho_ref = float(delta), float(rho_ref)
@@ -233,7 +205,7 @@ def so_masses(pm, centres, pos, delta, rho_ref, mass=None, rmin=None, rmax=None,
         error = ValueError('nbins must be in 2 .. %d (PMX_PAIRS_ROWS_MAX_BINS)' % MAX_BINS)
     if error is None:
         edges = numpy.concatenate([[0.0], numpy.geomspace(rmin, rmax, nbins)])
-    _together(pm.comm, error)
+    together(pm.comm, error)
     prof = radial_profiles(pm, centres, pos, edges, mass=mass)
     dev = prof.mass.device
     nc = prof.mass.shape[0]

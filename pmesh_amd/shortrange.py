@@ -38,23 +38,21 @@ Units.  ``examples/nbody.py`` solves ``laplace(phi) = rho`` with mean density 1:
     acc = short_range_force(pm, pos, r_split, mass=m, G=1 / (4 * numpy.pi))       # + the readout of
     mesh = [rho_k.apply(Transfer.long_range(d, r_split)).c2r() for d in range(3)]  # these at pos
 
-On one rank the rows are sorted into one periodic cell grid of side >= r_cut (``fof.cell_grid`` / ``fof.cell_sort``;
-the auto form sorts once) and one kernel sums.  On several ranks the routing is that of pair_counts: the primaries go to
-their owners (``pm.decompose`` without ghosts), the sources and their masses to every rank whose block they lie within
-r_cut of; each rank sums the force on its primaries, and ``Layout.gather(mode='sum')`` returns the rows to their
-callers: every primary has one owner, so nothing is added twice.
+Host: the routing of DESIGN.md §5.7.0 (``_cells.Neighbourhood``) with the radius r_cut; the sources' masses travel with
+them, each rank sums the force on its primaries with one kernel, and the rows return to their callers with the mode
+'sum': every primary has one owner, so nothing is added twice.
 """
 import numpy
 import torch
 
 from . import backend
-from .fof import MAX_ROWS, _block, _rows, _together, cell_grid, cell_sort
+from ._cells import Neighbourhood, box_of, read_rows, refuse_not_finite, sorted_sets, together, within_reach
 
 RCUT = 4.5                               # the default r_cut in units of r_split (Gadget's RCUT)
 
 
 def local_force(be, pos1, pos2, mass2, grid, box, G, r_split, rc2, eps2, potential=False, neighbours=False):
-    """The sums of the rows of one rank on the cell grid `grid` (of fof.cell_grid): the force on every row of `pos1`
+    """The sums of the rows of one rank on the cell grid `grid` (of _cells.cell_grid): the force on every row of `pos1`
     from the rows of `pos2` with the masses `mass2` (pos2 None: from pos1 itself, mass2 then its masses).  Returns (acc
     (n1, 3), pot (n1,) or None, neighbours (n1,) or None) in the row order of pos1."""
     dev = pos1.device
@@ -62,11 +60,7 @@ def local_force(be, pos1, pos2, mass2, grid, box, G, r_split, rc2, eps2, potenti
     acc = torch.empty((n1, 3), dtype=torch.float64, device=dev)
     pot = torch.empty(n1, dtype=torch.float64, device=dev) if potential else None
     nb = torch.empty(n1, dtype=torch.int64, device=dev) if neighbours else None
-    _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
-    if pos2 is None:
-        order2, cell_start2, spos2 = order1, cell_start1, spos1
-    else:
-        _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
+    spos1, order1, cell_of1, spos2, order2, cell_start2 = sorted_sets(be, pos1, pos2, grid, box)
     be.short_range(spos1, order1, cell_of1, spos2, order2, cell_start2, mass2, grid[0], grid[3], box, G, r_split, rc2,
                    eps2, acc, pot, nb)
     return acc, pot, nb
@@ -98,21 +92,20 @@ def short_range_force(pm, pos, r_split, r_cut=None, mass=None, pos2=None, mass2=
     pos2, mass2 : the rows and masses of the sources, or None: `pos` and `mass`.  mass2 needs pos2.
     softening : the Plummer softening length.  G : the constant of gravity.
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them.
     """
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
     if nd != 3:
         raise NotImplementedError('the short-range force needs a mesh of three dimensions, not %d' % nd)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     auto = pos2 is None
     rs, error = _positive(r_split, 'r_split')
     rc = eps = g = None
     if error is None:
         rc, error = _positive(RCUT * rs if r_cut is None else r_cut, 'r_cut')
-    if error is None and not 2 * rc <= min(box):
+    if error is None and not within_reach(rc, box):
         error = ValueError('r_cut must be at most half the shortest box side: %r' % rc)
     if error is None:
         eps, error = _positive(softening, 'softening', zero=True)
@@ -125,50 +118,20 @@ def short_range_force(pm, pos, r_split, r_cut=None, mass=None, pos2=None, mass2=
             error = ValueError('G must be a finite number, not %r' % (G,))
     if error is None and auto and mass2 is not None:
         error = ValueError('mass2 needs pos2')
-    rows = []
-    for what, x, ncol, of in (('pos', pos, nd, None), ('pos2', pos2, nd, None), ('mass', mass, 1, 0),
-                              ('mass2', mass2, 1, 1)):
-        t = None
-        if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
-        rows.append(t)
-    _together(comm, error)
-    pos, pos2, mass, mass2 = rows
+    wanted = (('pos', pos, nd, None), ('pos2', pos2, nd, None), ('mass', mass, 1, 0), ('mass2', mass2, 1, 1))
+    (pos, pos2, mass, mass2), error = read_rows(pm, be, wanted, error)
+    together(comm, error)
     if mass is not None:
         mass = mass.reshape(-1)
     if mass2 is not None:
         mass2 = mass2.reshape(-1)
-    nbad = int((~torch.isfinite(pos)).any(dim=1).sum()) + (0 if auto else int((~torch.isfinite(pos2)).any(dim=1).sum()))
-    if comm.size > 1:
-        nbad = int(comm.allreduce(nbad))
-    if nbad:
-        raise ValueError('%d rows of pos and pos2 have a coordinate that is not finite' % nbad)
-    n1 = pos.shape[0]
+    refuse_not_finite(comm, 'pos and pos2', pos, pos2)
     src, msrc = (pos, mass) if auto else (pos2, mass2)
     rc2, eps2 = rc * rc, eps * eps
-    if comm.size == 1:
-        most = max(n1, src.shape[0])
-        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-        acc, pot, nb = local_force(be, pos, None if auto else src, msrc, cell_grid(most, rc, box), box, g, rs, rc2,
-                                   eps2, potential, neighbours)
-    else:
-        # the routing of pair_counts: the primaries to their owners, the sources to every rank whose block they lie
-        # within r_cut of (a hair more: a pair just inside r_cut across a block face must not depend on the rounding
-        # of the routing)
-        own = pm.decompose(pos, smoothing=0)
-        smoothing = rc * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-        ghosts = pm.decompose(src, smoothing=smoothing)
-        most = max(own.recvlength, ghosts.recvlength)
-        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
-        p1 = own.exchange(pos)
-        p2 = ghosts.exchange(src)
-        q2 = ghosts.exchange(msrc) if msrc is not None else None
-        lo, hi = _block(pm)
-        acc, pot, nb = local_force(be, p1, p2, q2, cell_grid(most, rc, box, lo, hi), box, g, rs, rc2, eps2, potential,
-                                   neighbours)
-        # every primary has exactly one owner: the sum over its copies is its value
-        acc = own.gather(acc, mode='sum')
-        pot = own.gather(pot, mode='sum') if potential else None
-        nb = own.gather(nb, mode='sum') if neighbours else None
+    hood = Neighbourhood(pm, rc, pos, pos2)
+    p1, p2, q2 = hood.to_owners(pos), hood.to_sources(src), hood.to_sources(msrc)
+    acc, pot, nb = local_force(be, p1, None if hood.same else p2, q2, hood.grid, box, g, rs, rc2, eps2, potential,
+                               neighbours)
+    acc, pot, nb = [hood.to_callers(x, 'sum') for x in (acc, pot, nb)]
     out = (acc,) + ((pot,) if potential else ()) + ((nb,) if neighbours else ())
     return out[0] if len(out) == 1 else out

@@ -64,6 +64,7 @@ import numpy
 import torch
 
 from . import backend
+from ._cells import box_of
 from .paircount import MAX_BINS, PairCounts, _binning, _count, _edges
 
 MODES = ('1d', '2d', 'projected', 'angular')
@@ -197,7 +198,7 @@ def survey_pair_counts(pm, pos1, edges, observer=None, pos2=None, weight1=None, 
     together.
     """
     nd = len(pm.Nmesh)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     e, sub, e2, given, b, R, error = _survey_binning(nd, edges, mode, muedges, Nmu, piedges, pimax, thetaedges, box)
     obs = None
     if error is None:

@@ -43,17 +43,16 @@ The rule (normative; include/pmesh_amd.h restates it next to the entry point).
 ``normalized()`` is ``zeta_l (2 l + 1) / (4 pi)^2``, the ``sum_m a_lm a*_lm / (4 pi)`` normalisation of Slepian &
 Eisenstein's eq. 15.  nbodykit is not a dependency and no test pins agreement with it beyond this formula.
 
-On one rank both sets are sorted into one periodic cell grid of side >= b and one kernel sums.  On several ranks the
-routing is that of pair_counts: the primaries go to their owners, the secondaries to every rank whose block they lie
-within b of; every primary sees its whole neighbourhood on its owner, so one allreduce of the four arrays finishes it
-and nothing is subtracted afterwards.
+Host: the routing of DESIGN.md §5.7.0 (``_cells.Neighbourhood``) with the radius b and one kernel per rank.  Every
+primary sees its whole neighbourhood on its owner, so one allreduce of the three float arrays, packed, and one of
+npairs finish it, and nothing is subtracted afterwards.
 """
 import numpy
 import torch
 
 from . import _abi, backend
-from .fof import MAX_ROWS, _allsum, _block, _rows, _together, cell_grid, cell_sort
-from .paircount import _edges, bin_volumes
+from ._cells import Neighbourhood, allsum, box_of, read_rows, refuse_not_finite, sorted_sets, together, within_reach
+from .paircount import _edges, bin_volumes, too_many
 
 MAX_ELL = _abi.PMX_THREEPT_MAX_ELL
 MAX_BINS = _abi.PMX_THREEPT_MAX_BINS
@@ -90,7 +89,7 @@ def _poles(poles):
 
 
 def local_multipoles(be, pos1, w1, pos2, w2, grid, box, e2, lmax):
-    """The four arrays of the rows of one rank on the cell grid `grid` (of fof.cell_grid): the primaries `pos1` with
+    """The four arrays of the rows of one rank on the cell grid `grid` (of _cells.cell_grid): the primaries `pos1` with
     the secondaries `pos2` (None: pos1 itself).  e2: a device tensor.  Returns (zeta of the shape (lmax + 1, nr, nr),
     diag, wpairs, npairs)."""
     dev = pos1.device
@@ -99,11 +98,9 @@ def local_multipoles(be, pos1, w1, pos2, w2, grid, box, e2, lmax):
     diag = torch.zeros(nr, dtype=torch.float64, device=dev)
     wpairs = torch.zeros(nr, dtype=torch.float64, device=dev)
     npairs = torch.zeros(nr, dtype=torch.int64, device=dev)
-    _, cell_of1, cell_start1, order1, spos1, _ = cell_sort(be, pos1, grid, box)
+    spos1, order1, cell_of1, spos2, order2, cell_start2 = sorted_sets(be, pos1, pos2, grid, box)
     if pos2 is None:
-        order2, cell_start2, spos2, w2 = order1, cell_start1, spos1, w1
-    else:
-        _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos2, grid, box)
+        w2 = w1
     be.threept_multipoles(spos1, order1, cell_of1, w1, spos2, order2, cell_start2, w2, grid[0], grid[3], box, e2,
                           lmax, zeta, diag, wpairs, npairs)
     return zeta, diag, wpairs, npairs
@@ -115,7 +112,7 @@ def _power_sums(comm, w, n):
         total = float(comm.allreduce(n)) if comm.size > 1 else float(n)
         return total, total, total
     w = w.to(torch.float64)
-    s = _allsum(comm, torch.stack([w.sum(), (w * w).sum(), (w * w * w).sum()])).cpu()
+    s = allsum(comm, torch.stack([w.sum(), (w * w).sum(), (w * w * w).sum()])).cpu()
     return float(s[0]), float(s[1]), float(s[2])
 
 
@@ -129,47 +126,36 @@ def threept_multipoles(pm, pos, edges, poles=(0, 1, 2), pos2=None, weight=None, 
     pos2 : the rows both neighbours are taken from, or None: from pos.
     weight, weight2 : (n,) float rows, or None for 1.  weight2 needs pos2.
 
-    Argument errors are raised on every rank together.  More than 2^31 - 1 rows, ghosts included, on one rank raise
-    ValueError: slots are 32-bit.
+    Argument errors are raised on every rank together, the row limit of DESIGN.md §5.7.0 among them.
     """
     be = backend.get()
     comm = pm.comm
     nd = len(pm.Nmesh)
     if nd != 3:
         raise NotImplementedError('three-point multipoles need a mesh of three dimensions, not %d' % nd)
-    box = [float(x) for x in numpy.broadcast_to(numpy.asarray(pm.BoxSize, dtype='f8'), (nd,))]
+    box = box_of(pm)
     auto = pos2 is None
     e, error = _edges(edges, 'edges')
     b = None
-    if error is None and len(e) - 1 > MAX_BINS:
-        error = ValueError('%d bins: at most %d (PMX_THREEPT_MAX_BINS)' % (len(e) - 1, MAX_BINS))
+    if error is None:
+        error = too_many(e, None, MAX_BINS, '(PMX_THREEPT_MAX_BINS)')
     if error is None:
         b = float(e[-1])
-        if not (numpy.isfinite(b) and b > 0 and 2 * b <= min(box)):
+        if not within_reach(b, box):
             error = ValueError('the largest separation must be finite, positive and at most half the shortest box '
                                'side: %r' % b)
     if error is None:
         poles, error = _poles(poles)
     if error is None and auto and weight2 is not None:
         error = ValueError('weight2 needs pos2')
-    rows = []
-    for what, x, ncol, of in (('pos', pos, nd, None), ('pos2', pos2, nd, None), ('weight', weight, 1, 0),
-                              ('weight2', weight2, 1, 1)):
-        t = None
-        if x is not None and error is None:
-            t, error = _rows(pm, be, x, what, ncol, None if of is None else rows[of].shape[0])
-        rows.append(t)
-    _together(comm, error)
-    pos, pos2, weight, weight2 = rows
+    wanted = (('pos', pos, nd, None), ('pos2', pos2, nd, None), ('weight', weight, 1, 0), ('weight2', weight2, 1, 1))
+    (pos, pos2, weight, weight2), error = read_rows(pm, be, wanted, error)
+    together(comm, error)
     if weight is not None:
         weight = weight.reshape(-1)
     if weight2 is not None:
         weight2 = weight2.reshape(-1)
-    nbad = int((~torch.isfinite(pos)).any(dim=1).sum()) + (0 if auto else int((~torch.isfinite(pos2)).any(dim=1).sum()))
-    if comm.size > 1:
-        nbad = int(comm.allreduce(nbad))
-    if nbad:
-        raise ValueError('%d rows of pos and pos2 have a coordinate that is not finite' % nbad)
+    refuse_not_finite(comm, 'pos and pos2', pos, pos2)
     n1 = pos.shape[0]
     sums1 = _power_sums(comm, weight, n1)
     W1 = sums1[0]
@@ -181,29 +167,16 @@ def threept_multipoles(pm, pos, edges, poles=(0, 1, 2), pos2=None, weight=None, 
     lmax = max(poles)
     dev = be.device
     e2 = torch.from_numpy(e * e).to(dev)
-    if comm.size == 1:
-        most = max(n1, 0 if auto else pos2.shape[0])
-        _together(comm, ValueError('more than 2^31 - 1 rows on one rank') if most > MAX_ROWS else None)
-        sums = local_multipoles(be, pos, weight, pos2, weight2, cell_grid(most, b, box), box, e2, lmax)
-    else:
-        # the routing of pair_counts: the primaries to their owners, the secondaries to every rank whose block they lie
-        # within b of (a hair more: a pair at exactly b across a block face must not depend on the routing's rounding)
-        own = pm.decompose(pos, smoothing=0)
-        smoothing = b * numpy.asarray(pm.Nmesh, dtype='f8') / numpy.asarray(box) * (1 + 1e-9)
-        ghosts = pm.decompose(pos if auto else pos2, smoothing=smoothing)
-        most = max(own.recvlength, ghosts.recvlength)
-        _together(comm, ValueError('more than 2^31 - 1 rows and ghosts on one rank') if most > MAX_ROWS else None)
-        p1 = own.exchange(pos)
-        q1 = own.exchange(weight) if weight is not None else None
-        p2 = ghosts.exchange(pos if auto else pos2)
-        w2 = weight if auto else weight2
-        q2 = ghosts.exchange(w2) if w2 is not None else None
-        lo, hi = _block(pm)
-        sums = local_multipoles(be, p1, q1, p2, q2, cell_grid(most, b, box, lo, hi), box, e2, lmax)
+    hood = Neighbourhood(pm, b, pos, pos2)
+    p1, q1 = hood.to_owners(pos), hood.to_owners(weight)
+    p2, q2 = hood.to_sources(pos if auto else pos2), hood.to_sources(weight if auto else weight2)
+    sums = local_multipoles(be, p1, q1, None if hood.same else p2, q2, hood.grid, box, e2, lmax)
+    if comm.size > 1:
+        # the three float arrays travel as one
         nr = len(e) - 1
-        flat = _allsum(comm, torch.cat([sums[0].reshape(-1), sums[1], sums[2]]))
+        flat = hood.allsum(torch.cat([sums[0].reshape(-1), sums[1], sums[2]]))
         nz = (lmax + 1) * nr * nr
-        sums = (flat[:nz].reshape(lmax + 1, nr, nr), flat[nz:nz + nr], flat[nz + nr:], _allsum(comm, sums[3]))
+        sums = (flat[:nz].reshape(lmax + 1, nr, nr), flat[nz:nz + nr], flat[nz + nr:], hood.allsum(sums[3]))
     zeta, diag, wpairs, npairs = sums
     zeta = zeta[list(poles)].contiguous()
     return ThreePoint(zeta, diag, wpairs, npairs, poles, e, auto, box, W1, W2, W2sq, W3)
