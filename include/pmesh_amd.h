@@ -1095,7 +1095,7 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * pmesh_amd.pairlabels).  They are flag bits above the base modes: the valid modes are PMX_PAIRS_SPLIT | m (16 .. 20)
  * and PMX_PAIRS_JACKKNIFE | m (32 .. 36), m one of the base modes PMX_PAIRS_1D, PMX_PAIRS_2D, PMX_PAIRS_PROJECTED,
  * PMX_PAIRS_2D_MIDPOINT and PMX_PAIRS_PROJECTED_MIDPOINT; 10 to 15, 21 to 31 and 37 to 127 are PMX_EINVAL, and so is
- * everything from 128 on but the two alignment modes 128 and 130 described further below.
+ * everything from 128 on but the two alignment modes 128 and 130 and the moments mode 517 described further below.
  *   shared    rows, wrapping, the minimum image, r2, q, the squared edges, the r-, mu- and pi-bin and the pimax cut are
  *             exactly those of the base mode m, with its ndim (1 to 3 for 1D, three dimensions otherwise), its los and
  *             its sub; all arithmetic in double, every operation rounded once, no contraction, no square root choosing
@@ -1129,7 +1129,7 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  * and w_++(rp): halotools-ia's ed_3d, ee_3d, gi_plus_projected, ii_plus_projected and their minus partners;
  * pmesh_amd.alignments).  PMX_PAIRS_ALIGN is a flag bit above the base modes: the valid modes are PMX_PAIRS_ALIGN |
  * PMX_PAIRS_1D (128) and PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED (130); 129, 131, 132, 128 | 16, 128 | 32 and everything
- * from 133 on are PMX_EINVAL.  Mode 128 shares everything below with PMX_PAIRS_1D, mode 130 with PMX_PAIRS_PROJECTED:
+ * from 133 on (but the moments mode 517) are PMX_EINVAL.  Mode 128 shares everything below with PMX_PAIRS_1D, mode 130 with PMX_PAIRS_PROJECTED:
  *   shared    rows, wrapping, the minimum image dx_d (primary minus secondary), r2, q, the squared edges, the r-bin, the
  *             pi-bin, the pimax cut and the loop over windows of 2^23 secondaries; all arithmetic in double; every
  *             operation rounded once, no contraction; no square root chooses a bin.  npairs equals npairs of the base
@@ -1166,7 +1166,46 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
  *             products a2 * r2 and a2 * c2 must neither overflow nor underflow: finite, sanely scaled columns are the
  *             caller's business.
  *   LDS       the histogram of a workgroup holds a 32-bit count and 2 + NS doubles per bin (pmx_pairs_align.hip): 44 KB
- *             in mode 128, 68 KB in mode 130 at PMX_PAIRS_ALIGN_MAX_BINS bins. */
+ *             in mode 128, 68 KB in mode 130 at PMX_PAIRS_ALIGN_MAX_BINS bins.
+ *
+ * The mode with moment sums per primary row (the inertia tensor, axis ratios and major axis, the centre-of-mass offset,
+ * the velocity dispersion, the angular momentum and the spin of the sources inside spheres about every centre: the
+ * shape and spin columns of a halo catalogue; pmesh_amd.moments).  PMX_PAIRS_MOMENTS is a flag bit above the row mode:
+ * the only valid mode is PMX_PAIRS_MOMENTS | PMX_PAIRS_1D_ROWS (517).  512 alone, 512 | m for every other m in 0 .. 7
+ * and 512 combined with 16, 32 or 128 are PMX_EINVAL.  ndim 2 or 3 (1 is PMX_EINVAL), nsub == 1, sub == NULL.
+ *   shared    rows, wrapping, the minimum image, the arrays in the caller's row order that are added to, the windows of
+ *             2^23 secondaries and the absent row identity are those of PMX_PAIRS_1D_ROWS.  For the primary row i and
+ *             the secondary j: dx_d is what the row mode forms, centre minus source, minimum image; q = sum_d dx_d^2
+ *             from 0 in ascending d, in double, every operation rounded once, no contraction; s_d = -dx_d (exact) is
+ *             the source as seen from the centre.
+ *   columns   weight1 is required: 2 columns (w_i, s2_i), s2_i the square of the centre's scale, finite and positive
+ *             (the caller's business: a row with another s2 counts nothing or nonsense, and indexes nothing).  weight2
+ *             is required: 1 column (m_j), or 1 + ndim columns (m_j, v_0 .. v_{ndim-1}).  Float or double, in ROW order,
+ *             read through order1 / order2.  Any other column count, or a missing vec, is PMX_EINVAL.
+ *   bins      the edges of row i are E_k = e2[k] * s2_i, one rounding each.  The pair is in bin k when E_k <= q <
+ *             E_{k + 1}; it is not counted when q < E_0 or q >= E_nr: the comparisons of the base modes on E in place
+ *             of e2.  With s2_i == 1.0 the bins are bit for bit those of PMX_PAIRS_1D_ROWS.
+ *   limit     nr <= PMX_PAIRS_MOMENTS_MAX_BINS, else PMX_EINVAL.
+ *   sums      per row i and bin b, with m = w_i * m_j (one rounding): npairs[i * nr + b] += 1 (exact, as in the row
+ *             modes); wnpairs[i * nr + b] += m; rsum[(i * nr + b) * NS + k] += the k-th of, in this order,
+ *               m * sqrt(q)
+ *               m * s_d, d ascending
+ *               m * s_a * s_b for a <= b, in the order 00, 01, 02, 11, 12, 22 (ndim 2: 00, 01, 11): NT = ndim (ndim +
+ *                 1) / 2 of them
+ *               the reduced tensor in the same order, (m * s_a * s_b) / q, the term 0 where q == 0
+ *             and, where weight2 has velocities,
+ *               m * v_d, d ascending
+ *               m * (sum_d v_d^2)
+ *               m * (s x v): (s_1 v_2 - s_2 v_1, s_2 v_0 - s_0 v_2, s_0 v_1 - s_1 v_0) in three dimensions, NL = 3;
+ *                 s_0 v_1 - s_1 v_0 in two, NL = 1.
+ *             NS = 1 + ndim + 2 NT without velocities and ndim + 1 + NL more with them: 16 or 23 doubles per (row, bin)
+ *             in three dimensions, 9 or 13 in two.  rsum has NS * n1 * nr entries.  The double sums have no fixed
+ *             order; within a term the operations may be contracted or regrouped (the kernel forms m / q once per
+ *             pair): a term carries at most four roundings.  A source that coincides with a centre is a pair at q ==
+ *             0: counted in bin 0 when e2[0] == 0, with s == 0 and its reduced term 0.
+ *   LDS       one wave per primary row keeps its scaled edges and its histogram, a 32-bit count and 1 + NS doubles per
+ *             slot over PMX_PAIRS_MOMENTS_MAX_BINS slots (bins x copies), in LDS: 51 KB per workgroup of four waves at
+ *             23 sums (pmx_pairs_moments.hip). */
 #define PMX_PAIRS_MAX_BINS 4096         /* nr, nr * nmu or nrp * npi of one call (nbodykit's habitual 40 x 100 fits) */
 #define PMX_PAIRS_1D 0                   /* `mode`: bins of r */
 #define PMX_PAIRS_2D 1                   /* bins of (r, mu) */
@@ -1185,6 +1224,8 @@ int pmx_fof_group_sums(int32_t ndim, int64_t n, const pmx_vec *pos, const int64_
 #define PMX_PAIRS_LABEL_SLOTS 4096
 #define PMX_PAIRS_ALIGN      128  /* | PMX_PAIRS_1D (128) or PMX_PAIRS_PROJECTED (130): intrinsic-alignment sums */
 #define PMX_PAIRS_ALIGN_MAX_BINS 1024    /* nr * nsub of one call in these two modes */
+#define PMX_PAIRS_MOMENTS    512  /* | PMX_PAIRS_1D_ROWS (517): moment sums per primary row, bins in units of its scale */
+#define PMX_PAIRS_MOMENTS_MAX_BINS 64    /* nr of one call in that mode */
 
 /* npairs[b], wnpairs[b], rsum[b] += the sums over the pairs of bin b (DEVICE int64 / double / double arrays of
  * nr * nsub entries; the caller zeroes them, or keeps adding).  One entry, one kernel.

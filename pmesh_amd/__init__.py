@@ -26,6 +26,7 @@
     from pmesh_amd.pairlabels import pair_counts_split, pair_correlation_split, box_regions   # the one-halo / two-halo split; sub-box labels
     from pmesh_amd.alignments import alignment_counts, projected_alignment_counts   # intrinsic alignments: omega(r), eta(r), w_g+(rp), w_++(rp)
     from pmesh_amd.alignments import ellipticity_from_orientation   # the projected spin-2 ellipticity of a 3-d axis
+    from pmesh_amd.moments import radial_moments, halo_shapes, ellipticity_from_shapes   # per-centre moment sums: halo shapes, spins and dispersions
     from pmesh_amd.lpt import lpt, lpt1, lpt2source  # 1LPT / 2LPT displacements of initial conditions
     from pmesh_amd.lpt import lpt_vjp, lpt_jvp, lpt2source_vjp, lpt2source_jvp   # and their gradients
 

@@ -59,8 +59,8 @@ are those of pmesh_amd.paircount (rule 8 and the routing there).
     pa.w('plus1')                                                  # w_g+(rp): shapes in set 1, positions in set 2
     pa.w('plusplus'), pa.w('crosscross'), pa.w('cross1')           # w_++, w_xx and the null test w_gx (ellip2 given)
 
-Out of scope: the survey forms, whose line of sight is the observer's; jackknife combinations of these sums; measuring
-the shapes of FoF groups: the caller brings the orientations.
+Out of scope: the survey forms, whose line of sight is the observer's; jackknife combinations of these sums.  The
+caller brings the orientations: pmesh_amd.moments.halo_shapes measures them about the centres of a halo catalogue.
 """
 import numpy
 import torch

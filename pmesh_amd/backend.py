@@ -502,7 +502,10 @@ class HipBackend(object):
         have 2 (split) or 1 + 2 K (jackknife, K = (PMX_PAIRS_LABEL_SLOTS / nbins - 2) / 2) blocks of nbins entries,
         `rsum` 2 or 1.  In the two alignment modes (PMX_PAIRS_ALIGN | PMX_PAIRS_1D, PMX_PAIRS_ALIGN | PMX_PAIRS_PROJECTED)
         they are the (n, 1 + ndim) blocks (w, a) or the (n, 3) blocks (w, g1, g2), and `rsum` has 4 or 7 times nr * nsub
-        entries"""
+        entries.  In the moments mode (PMX_PAIRS_MOMENTS | PMX_PAIRS_1D_ROWS) weight1 is the (n1, 2) block (w, s2),
+        weight2 the (n2, 1) block (m) or the (n2, 1 + ndim) block (m, v), `sub` is None, `npairs` and `wnpairs` have
+        n1 * nr entries and `rsum` NS * n1 * nr, NS = 1 + ndim + ndim (ndim + 1), with velocities ndim + 1 + (3 if ndim
+        == 3 else 1) more"""
         if spos1.shape[0] == 0 or spos2.shape[0] == 0:
             return
         if int(mode) in (_abi.PMX_PAIRS_1D_VELOCITY, _abi.PMX_PAIRS_PROJECTED_VELOCITY, _abi.PMX_PAIRS_1D_LOS):
@@ -521,6 +524,23 @@ class HipBackend(object):
             for w, s in ((weight1, spos1), (weight2, spos2)):
                 if w is None or w.dim() != 2 or w.shape[0] != s.shape[0]:
                     raise ValueError('the alignment modes need weight1 and weight2 as (n, ncol) blocks of the rows')
+        if int(mode) == _abi.PMX_PAIRS_MOMENTS | _abi.PMX_PAIRS_1D_ROWS:
+            # the moments mode: (n1, 2) against (n2, 1) or (n2, 1 + ndim); rsum of NS * n1 * nr entries; no sub axis
+            nd, n1, nr = spos1.shape[1], spos1.shape[0], e2.numel() - 1
+            if sub is not None:
+                raise ValueError('the moments mode takes no sub axis')
+            if nr > _abi.PMX_PAIRS_MOMENTS_MAX_BINS:
+                raise ValueError('the moments mode takes at most %d bins' % _abi.PMX_PAIRS_MOMENTS_MAX_BINS)
+            if weight1 is None or weight1.dim() != 2 or tuple(weight1.shape) != (n1, 2):
+                raise ValueError('the moments mode needs weight1 as the (n1, 2) block (w, s2)')
+            if weight2 is None or weight2.dim() != 2 or weight2.shape[0] != spos2.shape[0] \
+                    or weight2.shape[1] not in (1, 1 + nd):
+                raise ValueError('the moments mode needs weight2 as the (n2, 1) block (m) or the (n2, 1 + ndim) block '
+                                 '(m, v)')
+            nsums = 1 + nd + nd * (nd + 1) + ((nd + 1 + (3 if nd == 3 else 1)) if weight2.shape[1] > 1 else 0)
+            if rsum.numel() < nsums * n1 * nr or min(npairs.numel(), wnpairs.numel()) < n1 * nr:
+                raise ValueError('the moments mode needs npairs and wnpairs of n1 * nr entries and rsum of %d * n1 * nr'
+                                 % nsums)
         split, jack = int(mode) & ~7 == _abi.PMX_PAIRS_SPLIT, int(mode) & ~7 == _abi.PMX_PAIRS_JACKKNIFE
         if split or jack:
             # the modes by row labels: (n, 2) blocks (w, label); 2 or 1 + 2 K blocks of nbins entries (rsum: 2 or 1)

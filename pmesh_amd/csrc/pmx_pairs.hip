@@ -19,6 +19,7 @@
 //   pmx_pairs_vel.hip       PMX_PAIRS_1D_VELOCITY, _PROJECTED_VELOCITY, _1D_LOS: pairwise velocity sums
 //   pmx_pairs_labels.hip    PMX_PAIRS_SPLIT | m, PMX_PAIRS_JACKKNIFE | m, m a base mode 0 .. 4: by row labels
 //   pmx_pairs_align.hip     PMX_PAIRS_ALIGN | PMX_PAIRS_1D, | PMX_PAIRS_PROJECTED: intrinsic-alignment sums
+//   pmx_pairs_moments.hip   PMX_PAIRS_MOMENTS | PMX_PAIRS_1D_ROWS: moment sums per primary row, bins in its own scale
 #include "pmx_pairs_dev.h"
 
 namespace pmx {
@@ -69,7 +70,7 @@ template <int NDIM, int MODE> static void pairs_launch(const PArgs &a, bool weig
 }
 
 // What a mode word asks for (the header lists the valid ones), decoded once; pmx_pair_counts checks the call against it.
-enum { PAIRS_PLAIN, PAIRS_SURVEY, PAIRS_ROWS, PAIRS_VEL, PAIRS_LABELS, PAIRS_ALIGN };
+enum { PAIRS_PLAIN, PAIRS_SURVEY, PAIRS_ROWS, PAIRS_VEL, PAIRS_LABELS, PAIRS_ALIGN, PAIRS_MOMENTS };
 // per family: the most bins nr * nsub, what to say above them, and what to say of weights without the family's columns
 static const struct {
     int64_t max_bins;
@@ -83,7 +84,9 @@ static const struct {
     {PMX_PAIRS_LABEL_SLOTS / 4, "more than PMX_PAIRS_LABEL_SLOTS / 4 bins in a mode by row labels",
      "the modes by row labels need weight1 and weight2 of 2 columns (w, label)"},
     {PMX_PAIRS_ALIGN_MAX_BINS, "more than PMX_PAIRS_ALIGN_MAX_BINS bins",
-     "the alignment modes need weight1 and weight2 of 1 + ndim columns (projected: 3)"}};
+     "the alignment modes need weight1 and weight2 of 1 + ndim columns (projected: 3)"},
+    {PMX_PAIRS_MOMENTS_MAX_BINS, "more than PMX_PAIRS_MOMENTS_MAX_BINS bins per row in the moments mode",
+     "the moments mode needs weight1 of 2 columns (w, s2) and weight2 of 1 or 1 + ndim columns (m, v)"}};
 struct PairMode {
     int family;                                  // whose kernels count: the files listed above, a row of pair_families
     int base;                                    // how a pair is binned: one of the five base modes of pair_rule
@@ -92,6 +95,7 @@ struct PairMode {
     int32_t min_ndim;                            // the fewest dimensions otherwise, and what to say below them
     const char *ndim_text;
     int32_t ncol;                                // the columns weight1 and weight2 must both have; 0: both optional
+    int32_t ncol2;                               // the other count weight2 may have instead (the moments mode); 0: none
 };
 
 static bool pair_mode(int32_t mode, int32_t ndim, PairMode &m)
@@ -111,6 +115,9 @@ static bool pair_mode(int32_t mode, int32_t ndim, PairMode &m)
     } else if (flags == PMX_PAIRS_ALIGN && (under == PMX_PAIRS_1D || under == PMX_PAIRS_PROJECTED)) {
         m.family = PAIRS_ALIGN;                  // the flag above 1D or projected and nothing else
         m.base = under;
+    } else if (mode == (PMX_PAIRS_MOMENTS | PMX_PAIRS_1D_ROWS)) {
+        m.family = PAIRS_MOMENTS;                // the flag above 1D_ROWS and nothing else
+        m.base = PMX_PAIRS_1D;
     } else {
         return false;
     }
@@ -128,12 +135,20 @@ static bool pair_mode(int32_t mode, int32_t ndim, PairMode &m)
     } else if (m.family == PAIRS_ALIGN) {
         m.min_ndim = 2;
         m.ndim_text = "the alignment modes need two or three dimensions";
+    } else if (m.family == PAIRS_MOMENTS) {
+        m.min_ndim = 2;
+        m.ndim_text = "the moments mode needs two or three dimensions";
     }
     // the columns: (w, v_0 .. v_{ndim-1}), or (w, s) in the mode 1D_LOS; (w, label); (w, a_0 .. a_{ndim-1}) above 1D,
-    // (w, g1, g2) above projected
+    // (w, g1, g2) above projected; (w, s2) against (m) or (m, v_0 .. v_{ndim-1}) in the moments mode
     if (m.family == PAIRS_VEL) m.ncol = mode == PMX_PAIRS_1D_LOS ? 2 : 1 + ndim;
     if (m.family == PAIRS_LABELS) m.ncol = 2;
     if (m.family == PAIRS_ALIGN) m.ncol = m.base == PMX_PAIRS_PROJECTED ? 3 : 1 + ndim;
+    m.ncol2 = 0;
+    if (m.family == PAIRS_MOMENTS) {
+        m.ncol = 2;
+        m.ncol2 = 1 + ndim;
+    }
     return true;
 }
 
@@ -153,6 +168,7 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
                 "the modes 2D and projected need three dimensions and a line of sight along one of them");
     PMX_REQUIRE(ndim >= m.min_ndim, PMX_EINVAL, m.ndim_text);
     PMX_REQUIRE(nr >= 1 && nsub >= 1 && (!m.one || nsub == 1), PMX_EINVAL, "bad bin counts");
+    PMX_REQUIRE(m.family != PAIRS_MOMENTS || !sub, PMX_EINVAL, "the moments mode takes no sub axis: sub must be NULL");
     PMX_REQUIRE((int64_t)nr * nsub <= PMX_PAIRS_MAX_BINS, PMX_EINVAL, "more than PMX_PAIRS_MAX_BINS bins");
     PMX_REQUIRE((int64_t)nr * nsub <= pair_families[m.family].max_bins, PMX_EINVAL,
                 pair_families[m.family].bins_text);
@@ -165,8 +181,9 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
     const bool has1 = weight1 && weight1->data, has2 = weight2 && weight2->data;
     PMX_REQUIRE(!has1 || vec_ok(weight1), PMX_EINVAL, "weight1 must be float or double");
     PMX_REQUIRE(!has2 || vec_ok(weight2), PMX_EINVAL, "weight2 must be float or double");
-    PMX_REQUIRE(m.ncol == 0 || (has1 && has2 && weight1->ncol == m.ncol && weight2->ncol == m.ncol), PMX_EINVAL,
-                pair_families[m.family].ncol_text);
+    PMX_REQUIRE(m.ncol == 0 || (has1 && has2 && weight1->ncol == m.ncol &&
+                                (m.ncol2 ? weight2->ncol == 1 || weight2->ncol == m.ncol2 : weight2->ncol == m.ncol)),
+                PMX_EINVAL, pair_families[m.family].ncol_text);
     a.n1 = n1;
     a.n2 = n2;
     a.spos1 = spos1;
@@ -198,6 +215,7 @@ extern "C" int pmx_pair_counts(int32_t ndim, int32_t mode, int32_t los, int64_t 
         case PAIRS_VEL: pairs_vel_launch(a, ndim, mode, grid, st); break;
         case PAIRS_LABELS: pairs_labels_launch(a, ndim, mode, grid, st); break;
         case PAIRS_ALIGN: pairs_align_launch(a, ndim, mode, grid, st); break;
+        case PAIRS_MOMENTS: pairs_moments_launch(a, ndim, weight2->ncol > 1, st); break;
         default:
             if (m.base == PMX_PAIRS_2D) pairs_launch<3, PMX_PAIRS_2D>(a, weighted, grid, st);
             else if (m.base == PMX_PAIRS_PROJECTED) pairs_launch<3, PMX_PAIRS_PROJECTED>(a, weighted, grid, st);

@@ -301,5 +301,6 @@ void pairs_rows_launch(const PArgs &a, int ndim, int mode, bool weighted, hipStr
 void pairs_vel_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
 void pairs_labels_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
 void pairs_align_launch(const PArgs &a, int ndim, int mode, unsigned grid, hipStream_t st);
+void pairs_moments_launch(const PArgs &a, int ndim, bool vel, hipStream_t st);               // (one wave per primary)
 
 }  // namespace pmx

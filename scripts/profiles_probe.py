@@ -18,9 +18,18 @@ equal the baseline's counts: the probe stops otherwise.  One JSON line per workl
 library (PMESH_AMD_LIBRARY chooses another build: the A/B of -DPMX_ROWS_COPIES_MAX).  No threshold: the tests decide
 correctness.
 
+--moments times the moment sums of pmesh_amd.moments (csrc/pmx_pairs_moments.hip) instead, on the same workloads: per
+workload, with the one bin [0, b) and with 32 log bins, the mode PMX_PAIRS_MOMENTS | PMX_PAIRS_1D_ROWS without and with
+velocities (16 and 23 sums per centre and bin; unit scales, so the bins are those of the row mode) launched in turn
+with its yardstick, the weighted form of PMX_PAIRS_1D_ROWS (the kernel of the parent commit) on the same sorted rows,
+weights and edges: the median of --reps rounds and the spread (smallest and largest) of each, their ratios, and the
+ratio of LDS traffic per counted pair that would explain them, (1 + NS) doubles against 2.  The counts of both must be
+equal: the probe stops otherwise.  (PMESH_AMD_LIBRARY chooses another build: the A/B of -DPMX_MOMENTS_REDUCE.)
+
 Every workload runs in a process of its own under a time limit; the first that fails ends the run.
 
     python scripts/profiles_probe.py [--rows 16777216] [--centres 100000] [--mesh 256] [--reps 5] [--bins 32] [--limit 300]
+                                     [--moments]
 """
 import argparse
 import json
@@ -153,6 +162,85 @@ def probe(kind, seps, args):
     print(json.dumps(line), flush=True)
 
 
+def probe_moments(kind, seps, args):
+    import torch
+    from pmesh_amd import _abi, backend
+    from pmesh_amd.fof import cell_grid, cell_sort
+    from pmesh_amd.mock import lognormal_catalog
+    from pmesh_amd.moments import MOMENTS_MODE, moment_sums
+    from pmesh_amd.pm import ParticleMesh
+    from pmesh_amd.transfer import Tabulated
+    be = backend.get()
+    dev = be.device
+    pm = ParticleMesh([args.mesh] * 3, BoxSize=1000., dtype='f8')
+    kk = numpy.geomspace(1e-3, 20.0, 200)
+    p = 2e4 * kk / (1 + (kk / 0.02) ** 2) ** 1.4
+    tab = Tabulated(kk, numpy.sqrt(p / numpy.prod(pm.BoxSize)), loglog=True)
+    pos = lognormal_catalog(pm, tab, args.rows / float(numpy.prod(pm.BoxSize)), 42, bias=2.0).pos
+    torch.cuda.empty_cache()
+    n = pos.shape[0]
+    box = [float(x) for x in pm.BoxSize]
+    gen = torch.Generator(device=dev).manual_seed(7)
+    if kind == 'dense':
+        centres = pos[torch.randint(0, n, (args.centres,), generator=gen, device=dev)].clone()
+    else:
+        centres = torch.rand((args.centres, 3), generator=gen, device=dev, dtype=torch.float64) * box[0]
+    nc = centres.shape[0]
+    b = seps * (float(numpy.prod(box)) / n) ** (1 / 3.)
+    grid = cell_grid(max(n, nc), b, box)
+    _, cell_of1, _, order1, spos1, _ = cell_sort(be, centres, grid, box)
+    _, _, cell_start2, order2, spos2, _ = cell_sort(be, pos, grid, box)
+    slots = visited(cell_of1, cell_start2, grid[0])
+    f8 = torch.float64
+    w1 = torch.ones((nc, 2), dtype=f8, device=dev)                 # (w, s2) = (1, 1); its first column serves the row mode
+    w2 = torch.cat([torch.ones((n, 1), dtype=f8, device=dev),
+                    torch.randn((n, 3), generator=gen, dtype=f8, device=dev)], dim=1)
+    mass, unit = w2[:, :1].contiguous(), w1[:, :1].contiguous()
+    for bins in (1, args.bins):
+        edges = numpy.geomspace(b / 100, b, bins + 1) if bins > 1 else numpy.array([0.0, b])
+        nr = len(edges) - 1
+        e2 = torch.from_numpy(edges * edges).to(dev)
+        outs = {}
+        for name, ns in (('rows', 1), ('moments', moment_sums(3, False)), ('moments_vel', moment_sums(3, True))):
+            outs[name] = [torch.zeros((nc, nr), dtype=torch.int64, device=dev), torch.zeros((nc, nr), dtype=f8, device=dev),
+                          torch.zeros((nc, nr, ns), dtype=f8, device=dev)]
+
+        def launch(name):
+            mode, a1, a2 = {'rows': (_abi.PMX_PAIRS_1D_ROWS, unit, mass),
+                            'moments': (MOMENTS_MODE, w1, mass), 'moments_vel': (MOMENTS_MODE, w1, w2)}[name]
+            be.pair_counts(mode, 2, spos1, order1, cell_of1, a1, spos2, order2, cell_start2, a2, grid[0], grid[3], box,
+                           e2, None, *outs[name])
+        times = {name: [] for name in outs}
+        for rep in range(args.reps + 1):                           # (one warm-up round; the three in turn)
+            for name in outs:
+                if rep == 1:
+                    for x in outs[name]:
+                        x.zero_()
+                a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                launch(name)
+                z.record()
+                z.synchronize()
+                if rep:
+                    times[name].append(a.elapsed_time(z))
+        # (after the warm-up round the outputs were zeroed once and args.reps launches added to them)
+        assert torch.equal(outs['rows'][0], outs['moments'][0]) and torch.equal(outs['rows'][0], outs['moments_vel'][0]), \
+            'the counts of the moments mode are not those of the row mode'
+        counted = int(outs['rows'][0].sum()) // args.reps
+        line = {'centres': kind, 'mean_separations': seps, 'sources': n, 'ncentres': nc, 'b': round(b, 4), 'bins': nr,
+                'visited_slots': slots, 'counted_pairs': counted, 'library': os.environ.get('PMESH_AMD_LIBRARY', ''),
+                'build_flags': be.lib.pmx_build_flags().decode()}
+        med = {name: float(numpy.median(t)) for name, t in times.items()}
+        for name, t in times.items():
+            line[name + '_ms'] = round(med[name], 3)
+            line[name + '_spread_ms'] = [round(min(t), 3), round(max(t), 3)]
+            line[name + '_visited_pairs_per_s'] = round(slots / med[name] * 1e3, -6)
+        for name in ('moments', 'moments_vel'):
+            line[name + '_over_rows'] = round(med[name] / med['rows'], 2)
+        line['lds_traffic_ratio'] = [(1 + moment_sums(3, False)) / 2., (1 + moment_sums(3, True)) / 2.]
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=2 ** 24)
@@ -162,11 +250,12 @@ def main():
     ap.add_argument('--bins', type=int, default=32, help='log bins of r; 1: the one bin [0, b)')
     ap.add_argument('--workloads', nargs='+', default=['dense:2', 'dense:8', 'uniform:2', 'uniform:8'])
     ap.add_argument('--limit', type=int, default=300, help='seconds per workload')
+    ap.add_argument('--moments', action='store_true', help='time the moment sums next to the weighted row mode')
     ap.add_argument('--step', help='run this workload alone, in this process: <centres>:<mean separations>')
     args = ap.parse_args()
     if args.step:
         kind, seps = args.step.split(':')
-        probe(kind, float(seps), args)
+        (probe_moments if args.moments else probe)(kind, float(seps), args)
         return 0
     for step in args.workloads:
         # a fresh process per workload, under its own limit; after a failure nothing more is started
